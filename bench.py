@@ -3,13 +3,18 @@
 BASELINE.json workload, 4096 envs x 128 steps, synthetic Breakout-shaped
 (4x84x84 uint8) envs on the device, NatureCNN actor-critic, fp32.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
              --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one full PPO iteration over the 4096 x 128 rollout.  The total env
 count is fixed as N grows (strong scaling): rank g steps envs [g*4096/N, ...).
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, runs W warmup iterations, times K steps and prints the headline line
+(env-steps/s, ms_per_step, the per-phase times of the timed steps).  --full adds what takes runs
+of its own: the event-timed profiling iterations and per-kernel rooflines, the GAE kernel
+timings and the CPU baseline.  --dump-outputs DIR writes what the last timed step computed.
 """
 import argparse
 import json
@@ -274,6 +279,42 @@ def gae_large_n(dual, T=128, N=1 << 20, reps=10):
             "achieved": round(gbs, 1), "frac": round(gbs / HBM_PEAK_GBS, 4)}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(folder, arrays):
+    """--dump-outputs: every array of `arrays` (name -> numpy array or device tensor) as folder/<name>.npy
+    in float32 (float64 stays float64).  The files together stay under DUMP_BUDGET_BYTES: an array over its
+    share is written as a fixed sample of its flattened elements (sorted indices drawn without replacement
+    from RandomState(0), the same from run to run)."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        keep = share // a.itemsize
+        if a.size > keep:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(folder, name + ".npy"), a)
+
+
+def ppo_outputs(alg):
+    """What a caller of collect_samples() + train() receives from the last iteration: the updated
+    parameters (flat, in module order), the losses train() accumulated, and the rollout it trained on."""
+    ro = alg.rollout
+    out = {"policy_params": alg.flat.data[:alg.flat.n], "loss_accum": alg.loss_accum}
+    for extra in ("rnd_flat", "icm_flat"):
+        f = getattr(alg, extra, None)
+        if f is not None:
+            out[extra.replace("flat", "params")] = f.data[:f.n]
+    for k in ("actions", "log_probs", "rewards", "values", "masks", "advantages", "returns",
+              "int_rewards", "int_values", "int_advantages", "int_returns"):
+        if hasattr(ro, k):
+            out["rollout_" + k] = getattr(ro, k)
+    return out
+
+
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -286,7 +327,14 @@ def parse():
     p.add_argument("--nstep", type=int, default=128)
     p.add_argument("--epochs", type=int, default=10)
     p.add_argument("--batch-size", type=int, default=16384)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what takes runs of its own: event-timed profiling iterations and per-kernel "
+                        "rooflines, the GAE kernel timings, the CPU baseline (unless --no-cpu-baseline)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step computed (updated parameters, losses, "
+                        "the rollout's arrays) as DIR/<name>.npy, float32 / float64, at most 64 MB in all "
+                        "(rank 0's shard in a multi-rank run)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     p.add_argument("--cpu-threads", type=int, default=0)
     p.add_argument("--force-dist", action="store_true",
                    help="one rank: run the world > 1 code paths (owned-row minibatches, every collective) over a "
@@ -401,7 +449,7 @@ def main():
     import logger
 
     if args.algo == "es":
-        return bench_es(args, world, rank, tdist)
+        return bench_es(args, world, rank, tdist, json_out)
 
     env_id = {"ppo": "BreakoutNoFrameskip-v4", "icm": "BreakoutNoFrameskip-v4",
               "rnd": "MontezumaRevengeNoFrameskip-v4"}[args.algo]
@@ -432,9 +480,13 @@ def main():
     # largest kernel is the one rocprofv3's --stats ranks first ("roofline_rocprof"), whose event
     # durations include its sharing of the CUs with the other stream's kernels.
     solo, duo = {}, {}
-    # (with --warmup 1 one more untimed iteration runs for the two-stream pick; the line says so)
-    n_warm = max(args.warmup, 2 if streams else 1)
+    # (--full with --warmup 1: one more untimed iteration runs for the two-stream pick; the line says so.
+    # A plain run warms up with exactly --warmup iterations as the timed region runs them.)
+    n_warm = max(args.warmup, 2 if streams else 1) if args.full else args.warmup
     for w in range(n_warm):
+        if not args.full:
+            iteration()
+            continue
         convs.BWD_STREAMS = streams and w > 0
         if w == 0 or (w == 1 and streams):
             alg.collect_samples()
@@ -456,7 +508,8 @@ def main():
     # --stats's ranking over the timed region), the one-stream pick beside it
     prof_kernel = max(duo_tot, key=duo_tot.get) if any(duo_tot.values()) else solo_kernel
     gae_kernel = "ppox_gae" if args.algo != "rnd" else "ppox_gae_dual"
-    native.enable_event_timing([prof_kernel])
+    if args.full:
+        native.enable_event_timing([prof_kernel])
 
     phases.enable_timers()
     torch.cuda.synchronize()
@@ -469,12 +522,14 @@ def main():
     if world > 1:
         tdist.barrier()
     dt = time.perf_counter() - t0
-    kt = native.event_times_ms(prof_kernel)
+    kt = native.event_times_ms(prof_kernel) if args.full else []
     native.enable_event_timing([])
     phase_ms = {k: {"gpu_ms": round(v["gpu_ms"] / args.steps, 2), "host_ms": round(v["host_ms"] / args.steps, 2)}
                 for k, v in phases.summary().items()}
     phases.enable_timers(False)
-    gae_ms = gae_kernel_ms(alg, args.algo == "rnd")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ppo_outputs(alg))
+    gae_ms = gae_kernel_ms(alg, args.algo == "rnd") if args.full else None
     if world > 1:
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
@@ -558,7 +613,7 @@ def main():
         large = gae_large_n(gae_kernel != "ppox_gae")
         if large:
             out["gae_roofline"]["large_n"] = large
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         sys.path.insert(0, ROOT)
         from oracle.baseline import atari_ppo_iteration_rate
         out["cpu_baseline"] = atari_ppo_iteration_rate(args.envs, args.nstep, args.epochs, args.batch_size,
@@ -574,7 +629,7 @@ def main():
 FP64_VECTOR_PEAK_TFLOPS = 78.6  # AMD MI355X spec (FP64 vector); not listed in MI355X_MICROARCH.md
 
 
-def bench_es(args, world, rank, tdist):
+def bench_es(args, world, rank, tdist, json_out):
     """BASELINE.json config 5: ES-NSRA on Swimmer-v3 (synthetic SwimmerLike episodes of the
     Swimmer shape, 1000 steps), --population perturbations per generation, members sharded
     across ranks.  A step = one generation (noise, every member's episode, update, novelty
@@ -588,9 +643,11 @@ def bench_es(args, world, rank, tdist):
     hidden = [int(x) for x in args.es_hidden.split(",")]
     es = ES.EvolutionStrategy("Swimmer-v3", hidden_sizes=hidden, population_size=args.population, seed=1)
     logger.configure("bench", "Swimmer-v3", quiet=True)
-    native.enable_event_timing(["ppox_es_evaluate"])
+    if args.full:
+        native.enable_event_timing(["ppox_es_evaluate"])
     es.run(args.warmup, log_interval=10 ** 9)
-    native.enable_event_timing(["ppox_es_evaluate"])
+    if args.full:
+        native.enable_event_timing(["ppox_es_evaluate"])
     torch.cuda.synchronize()
     if world > 1:
         tdist.barrier()
@@ -604,8 +661,11 @@ def bench_es(args, world, rank, tdist):
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
         dt = float(t.item())
-    kt = [(ms, a) for ms, a in native.event_times_ms("ppox_es_evaluate") if a[3] > 1]  # population launches
+    kt = ([(ms, a) for ms, a in native.event_times_ms("ppox_es_evaluate") if a[3] > 1]  # population launches
+          if args.full else [])
     native.enable_event_timing([])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {f"weights_{i}": w for i, w in enumerate(es.weights)})
     steps = args.steps * args.population * es.T
     out = {"metric": "env-steps/sec (ES-NSRA: population episodes + update), Swimmer-v3 shape",
            "value": round(steps / dt, 1), "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,

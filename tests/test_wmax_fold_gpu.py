@@ -67,7 +67,9 @@ TAIL16 = 2 * (2 * 256 + 8)  # a packed form's tail (PACK_TAIL32 uint32) in int16
 
 def _same(x, y):
     if x.dtype != torch.int16:
-        return torch.equal(x, y)
+        # bit patterns, not float values: a form that this pass does not pack (wpd2 in split math) keeps its
+        # allocation's bytes, which may hold NaN patterns — equal bits, but never equal as floats
+        return torch.equal(x.view(torch.int32), y.view(torch.int32))
     t0 = x.numel() - TAIL16
     if not (torch.equal(x[:t0], y[:t0]) and torch.equal(x[t0 + 512:], y[t0 + 512:])):
         return False

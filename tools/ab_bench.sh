@@ -9,8 +9,8 @@ mkdir -p $O
 for rnd in 1 2; do
   for v in base "$@"; do
     if [ $v = base ]; then L=""; else L=tools/variants/$v/libppox.so; fi
-    PPOX_LIB=$L timeout -k 10 300 python -u bench.py --no-cpu-baseline --steps 10 --warmup 2 > $O/${v}_F$rnd.json 2>> $O/err.log || exit $?
-    PPOX_LIB=$L timeout -k 10 300 python -u bench.py --envs 512 --batch-size 2048 --steps 5 --warmup 2 --no-cpu-baseline \
+    PPOX_LIB=$L timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --steps 10 --warmup 2 > $O/${v}_F$rnd.json 2>> $O/err.log || exit $?
+    PPOX_LIB=$L timeout -k 10 300 python -u bench.py --full --envs 512 --batch-size 2048 --steps 5 --warmup 2 --no-cpu-baseline \
         > $O/${v}_R$rnd.json 2>> $O/err.log || exit $?
   done
 done

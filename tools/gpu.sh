@@ -29,7 +29,7 @@ RANK="--envs 512 --batch-size 2048"
 
 bench() {  # bench NAME OUTFILE ARGS...   (the step's VAR=value settings from $ENVS)
   local name=$1 out=$2; shift 2
-  env $ENVS timeout -k 10 400 python3 -u $R/bench.py "$@" > $O/$out.json 2>> $O/bench.err \
+  env $ENVS timeout -k 10 400 python3 -u $R/bench.py --full "$@" > $O/$out.json 2>> $O/bench.err \
       || { echo "bench $name failed" >&2; return 1; }
   cat $O/$out.json
 }

@@ -5,8 +5,8 @@
 set -o pipefail
 TAG=$1; SHAPES=$2; shift 2
 O=gpurun_out/abenv_$TAG; mkdir -p $O
-R="--envs 512 --batch-size 2048 --steps 5 --warmup 2 --no-cpu-baseline"
-F="--steps 4 --warmup 2 --no-cpu-baseline"
+R="--full --envs 512 --batch-size 2048 --steps 5 --warmup 2 --no-cpu-baseline"
+F="--full --steps 4 --warmup 2 --no-cpu-baseline"
 for P in $SHAPES; do
   timeout -k 10 200 python bench.py ${!P} > $O/${P}_base.json 2>>$O/e || exit $?
   i=0
