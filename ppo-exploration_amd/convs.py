@@ -276,9 +276,11 @@ class WmaxLink:
     weights it writes (ppox_adam_step_wmax) into bufs[nxt], which the packing zeroed beforehand; the next
     packing of those same weights (same step count, buffer and torch version counter) reads them and runs as one
     launch (ppox_nature_pack_all_wmax), zeroing the other buffer for the next step.  Anything else packs with its
-    own amax pass: weights written in place after the step (a torch in-place op on the flat buffer or a view of
-    it bumps the buffer's version counter, one through a weight Parameter — load_state_dict — the Parameter's;
-    both are part of the key), invalidate(), two steps without a packing between."""
+    own amax pass: weights written in place after the step (FlatParams.write_key: a torch in-place op on the flat
+    buffer or a view of it bumps the buffer's version counter, one through a weight Parameter — load_state_dict
+    — the Parameter's; a write that moves neither — x.data.copy_(), a native kernel or collective on the raw
+    buffer — is announced by FlatParams.touch(), whose generation number is part of the key too), invalidate(),
+    two steps without a packing between."""
 
     def __init__(self, flat, weights):
         base, n = flat.data.data_ptr(), flat.data.numel()
@@ -292,7 +294,7 @@ class WmaxLink:
         self.bufs = torch.zeros(2, native.WMAX_TENSORS * native.WMAX_SLOTS, dtype=torch.int32, device=flat.device)
         self.zeroed = [True, True]
         self.nxt = 0
-        self.valid = None  # (step count, data pointer, torch version, buffer) of the last recorded maxima
+        self.valid = None  # (the weights' write key, buffer) of the last recorded maxima
 
     def ready(self, flat):
         """the buffer the next step records into is zeroed"""
@@ -302,7 +304,7 @@ class WmaxLink:
         return self.bufs[self.nxt]
 
     def _key(self, flat):
-        return (flat.step_count, flat.data.data_ptr(), flat.data._version) + tuple(w._version for w in self.weights)
+        return flat.write_key(self.weights)
 
     def recorded(self, flat):
         self.valid = (self._key(flat), self.nxt)
@@ -371,7 +373,11 @@ class NatureConvs:
         self.px = self.h1p and PX and RELU_BITS
         self._ws = {}
         self._diag = None  # a dict: the backward keeps its intermediates there (tests)
+        # every parameter a packed form is derived from (the conv biases: the PX bias bounds in the forms' tails)
+        self._sources = (self.c1.weight, self.c2.weight, self.c3.weight, self.fc.weight, self.hid.weight,
+                         self.c1.bias, self.c2.bias, self.c3.bias)
         self._version = None
+        self._quick = None
         self._packed = set()
         self._last_batch = None
         self._forms_cache = {}
@@ -477,17 +483,31 @@ class NatureConvs:
             forms.add("qhd")
         return forms
 
-    def pack(self, batch=0, zero=None):
-        """Pack the weights (once per optimizer step) into the layouts the kernels of a
+    def weights_key(self):
+        """The key of the packed forms: it moves with every write to a parameter they are derived from that
+        FlatParams.write_key sees (an optimizer step, a torch in-place op on the flat buffer, a view of it or
+        a Parameter, FlatParams.touch())."""
+        return self.flat.write_key(self._sources)
+
+    def pack(self, batch=0, zero=None, in_pass=False):
+        """Pack the weights (once per write to them: FlatParams.write_key) into the layouts the kernels of a
         `batch`-row pass use; a later pass of another size packs only the forms still missing
         (one ppox_nature_pack_all call for the split and fc forms).  `zero` (int32 tensor) is
-        zeroed by that call when it runs: returns True if it did."""
-        v = (self.flat.step_count, self.flat.data.data_ptr())
+        zeroed by that call when it runs: returns True if it did.  in_pass: a call from inside a pass
+        whose forward_acts has already compared the full key (the fc layer, the heads, the dgrads) — it
+        compares the step count and touch() generation alone (plain ints: the torch version counters cost
+        ~0.1 us each, this runs several times per minibatch), so a pass runs on the weights as its
+        forward_acts found them."""
+        flat = self.flat
         key = (batch, HEAD_SPLIT_MIN_BATCH, HEAD_FWD_SPLITK, HEAD_BWD_SPLIT_MIN_BATCH, FC_SPLIT_MIN_BATCH)  # (tests patch these)
-        if v == self._version and key == self._last_batch:  # the hot path: several times per minibatch
+        if in_pass and key == self._last_batch and self._quick == (flat.step_count, flat.gen):
+            return False
+        v = flat.write_key(self._sources)
+        if v == self._version and key == self._last_batch:  # the hot path: once per pass
             return False
         if v != self._version:
             self._version, self._packed = v, set()
+            self._quick = (flat.step_count, flat.gen)
         self._last_batch = key
         forms = self._forms_cache.get(key)
         if forms is None:
@@ -528,6 +548,7 @@ class NatureConvs:
 
     def invalidate(self):
         self._version = None
+        self._quick = None
         self._packed = set()
         self._last_batch = None
         if self._wmax is not None:
@@ -569,7 +590,7 @@ class NatureConvs:
                 native.amax(y, out_am)
 
     def dgrad(self, layer, g, B, prev_act, out, am):
-        self.pack(B)  # the conv2 dgrad form depends on the batch
+        self.pack(B, in_pass=True)  # the conv2 dgrad form depends on the batch
         g_am, out_am = (am[AM_G3], am[AM_G2]) if layer == 3 else (am[AM_G2], am[AM_G1])
         if self.uses_split("dgrad", layer, B):
             bits = am.bits[layer - 2] if isinstance(am, PassState) else None
@@ -655,7 +676,7 @@ class NatureConvs:
         split over K below, rocBLAS on the NHWC-permuted weight below FC_SPLIT_MIN_BATCH.
         actor = (w, b): returns (f, logits), logits = f w^T + b computed by the split-K form's
         reduce (<= 8 actions) or None (the caller runs the actor head)."""
-        self.pack(h3.shape[0])
+        self.pack(h3.shape[0], in_pass=True)
         B = h3.shape[0]
         logits = None
         h3_exp = am.exp(EX_H3) if isinstance(am, PassState) else None

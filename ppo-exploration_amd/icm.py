@@ -84,8 +84,9 @@ class NativeIcm:
         return b[:n].view(shape)
 
     def pack(self):
-        """Split W1 into its f16 planes once per optimizer step."""
-        v = (self.flat.step_count, self.flat.data.data_ptr())
+        """Split W1 into its f16 planes once per write to it (an optimizer step, a torch in-place op on the
+        flat buffer, a view of it or the Parameter, FlatParams.touch(): FlatParams.write_key)."""
+        v = self.flat.write_key((self.w1,))
         if v != self._version:
             native.icm_pack_w1(self.w1.detach(), self.q)
             self._version = v

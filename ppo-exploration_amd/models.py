@@ -17,6 +17,7 @@ available (see convs.py); the small linear layers use PyTorch-ROCm (rocBLAS).
 """
 import contextlib
 import math
+import operator
 
 import numpy as np
 import torch
@@ -173,7 +174,7 @@ class CnnActorCritic(nn.Module):
         v = None
         if am is not None and cv is not None and cv.split_head(f.shape[0]):
             import convs as _convs
-            cv.pack(f.shape[0])
+            cv.pack(f.shape[0], in_pass=True)
             e = torch.empty_like(f)
             native.head_hidden_fwd(f, cv.qh[0], el.bias, e, amax_f=am[_convs.AM_F])
         elif am is not None and cv is not None and cv.split_head_fwd(f.shape[0]) and f.is_contiguous() \
@@ -181,7 +182,7 @@ class CnnActorCritic(nn.Module):
             # small batches: split over K, the critic head fused into the reduce when its weight is aligned
             import convs as _convs
             B = f.shape[0]
-            cv.pack(B)
+            cv.pack(B, in_pass=True)
             e = torch.empty_like(f)
             fuse = ce.weight.is_contiguous() and ce.weight.data_ptr() % 16 == 0
             v = (value_out if value_out is not None else torch.empty(B, device=f.device)) if fuse else None
@@ -449,6 +450,9 @@ class IntrinsicCuriosityModule(nn.Module):
         return torch.clamp((nh - fn).pow(2).mean(dim=-1), -5, 5)
 
 
+_VERSION = operator.attrgetter("_version")
+
+
 class FlatParams:
     """Re-homes a module's trainable parameters into one contiguous f32 device
     buffer (+ gradient and Adam moment buffers of the same layout).  Autograd
@@ -480,11 +484,27 @@ class FlatParams:
         for b in module.buffers():
             b.data = b.data.to(self.device)
         self.step_count = 0
+        self.gen = 0  # touch() calls
         # the NatureCNN weight packing whose amax pass the Adam step records (convs.WmaxLink; round 6)
         self.wmax = None
 
     def zero_grad(self):
         self.grad.zero_()
+
+    def touch(self):
+        """Announce a write to the parameters that torch's version counters do not see: x.data.copy_(), a
+        native kernel or a collective on the raw buffer (adam_step counts its own).  Every form derived from
+        the weights (convs.NatureConvs.pack, convs.WmaxLink, icm.NativeIcm.pack) is rebuilt at its next use.
+        Writes through torch — load_state_dict, an in-place op on a Parameter, on `data` or on a view of it —
+        move a counter and need no call."""
+        self.gen += 1
+
+    def write_key(self, tensors=()):
+        """A tuple that changes with every write to `tensors` (parameters of this buffer) that can be seen from
+        the host: the optimizer step count, the touch() generation, the buffer (its pointer and torch version
+        counter: in-place ops on it or a view of it) and each tensor's own version counter (in-place ops
+        through the Parameter, which does not share its buffer's counter)."""
+        return (self.step_count, self.gen, self.data.data_ptr(), self.data._version, *map(_VERSION, tensors))
 
     def adam_step(self, lr, max_grad_norm, betas=(0.9, 0.999), eps=1e-8):
         """clip_grad_norm_(max_grad_norm) + Adam.step (ppo.py:243-244)."""

@@ -347,7 +347,6 @@ def test_cnn_train_matches_reference_run(golden, name, math, rtol, head_min, mon
             np.testing.assert_allclose(float(init[k].double().sum()), float(f[p + "wsum0_" + k]), rtol=1e-5,
                                        atol=1e-5)
             v.copy_(init[k].to(v.device))
-    alg.policy.net.conv_impl.invalidate()
     ro = alg.rollout
     obs = f[p + "obs"]
     for t in range(T):
@@ -507,7 +506,6 @@ def test_cnn_train_16384_rows_matches_reference_run(golden, math, monkeypatch):
             init_diff[k] = float((init[k] - ref0).abs().max())
             init[k] = ref0
             v.copy_(ref0.to(v.device))
-    alg.policy.net.conv_impl.invalidate()
     ro = alg.rollout
     acts = f[p + "roll_actions"]
     crc = f[p + "obs_crc"]

@@ -123,10 +123,11 @@ def test_training_steps_fold_on_off_bitwise(monkeypatch):
     assert torch.equal(finals[0], finals[1])
 
 
-@pytest.mark.parametrize("how", ["parameter", "flat_view"])
+@pytest.mark.parametrize("how", ["parameter", "flat_view", "data_copy+touch"])
 def test_weights_written_after_the_step_pack_with_their_own_amax(monkeypatch, how):
     """weights overwritten in place between the step and the packing (a torch op on the flat buffer or a view of
-    it: load_state_dict, teacher forcing in test_c4_gpu.py) must not be packed from the step's stale partials"""
+    it: load_state_dict, teacher forcing in test_c4_gpu.py; or a write that moves no torch counter, announced by
+    FlatParams.touch()) must not be packed from the step's stale partials"""
     net, flat, cv = _net(6, True, monkeypatch)
     B = 2048
     cv.pack(B)
@@ -135,6 +136,12 @@ def test_weights_written_after_the_step_pack_with_their_own_amax(monkeypatch, ho
     with torch.no_grad():  # the fc weight's max moves: stale partials would pack wrong
         if how == "parameter":
             net.feature_extractor[7].weight.mul_(3.0)
+        elif how == "data_copy+touch":
+            w = net.feature_extractor[7].weight
+            key = cv._wmax._key(flat)
+            w.data.copy_(w.data * 3.0)
+            assert cv._wmax._key(flat) == key, "x.data.copy_() moves no counter"
+            flat.touch()
         else:
             w = net.feature_extractor[7].weight
             o = (w.data_ptr() - flat.data.data_ptr()) // 4
@@ -142,7 +149,7 @@ def test_weights_written_after_the_step_pack_with_their_own_amax(monkeypatch, ho
     folds = cv._wmax.folds
     cv.pack(B)
     torch.cuda.synchronize()
-    assert cv._wmax.folds == folds and cv._wmax.valid is None, "a version counter moved: its own amax pass"
+    assert cv._wmax.folds == folds and cv._wmax.valid is None, "a version counter or touch() moved the key: its own amax pass"
     got = _packed(cv)
     cv.invalidate()
     cv.pack(B)
