@@ -249,6 +249,44 @@ int ppox_vec_env_step(float* obs, const int32_t* actions, int64_t N, int32_t D,
                       int32_t* ep_len, float* done_ret, int32_t* done_len, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Device environments with real dynamics (csrc/env_real.hip; DESIGN.md "Real-dynamics
+ * envs" holds the equations).  Reset draws are Philox4x32-10 keyed by seed with counter
+ * (0 [control] or 0xFFFFFFFF [Catch], env_offset + n, episode index, 0xFFFFFFFF); a step
+ * that ends an episode records it, increments episode[n], redraws the state and writes
+ * the new episode's first observation (VecEnv auto-reset); the reward is the terminal
+ * step's.  done = terminated || ep_len + 1 >= max_len.
+ *
+ * Classic control, kind = PPOX_CONTROL_*: state (N, S) f64, episode (N,) i32, obs (N, D)
+ * f32 with (S, D) = CartPole (4, 4), MountainCar (2, 2), Acrobot (4, 6), Pendulum (2, 3).
+ * actions: (N,) int32 for the Discrete kinds, (N,) f32 torque for Pendulum.  ep_ret and
+ * ep_len are required; done_ret / done_len are nullable.
+ *
+ * Catch: obs (N, 4, 84, 84) u8 frame stacks (16B aligned, handled as ppox_atari_env_step's:
+ * older frames shifted, stack zeroed on done, new frame last); state (N, 4) i32 = ball
+ * column, ball row, ball dx, paddle column on a 12 x 12 grid of 7 x 7-pixel cells;
+ * actions (N,) int32 in {stay, left, right}.  Episodes last 11 steps; the last one's
+ * reward is +1 (caught) or -1.
+ * -------------------------------------------------------------------------*/
+#define PPOX_CONTROL_CARTPOLE 0
+#define PPOX_CONTROL_MOUNTAINCAR 1
+#define PPOX_CONTROL_ACROBOT 2
+#define PPOX_CONTROL_PENDULUM 3
+int ppox_control_env_reset(int32_t kind, double* state, int32_t* episode, float* obs, int64_t N,
+                           int64_t env_offset, uint64_t seed, float* ep_ret, int32_t* ep_len,
+                           void* stream);
+int ppox_control_env_step(int32_t kind, double* state, int32_t* episode, const void* actions,
+                          float* obs, int64_t N, int64_t env_offset, uint64_t seed,
+                          int32_t max_len, float* rewards, uint8_t* dones, float* ep_ret,
+                          int32_t* ep_len, float* done_ret, int32_t* done_len, void* stream);
+int ppox_catch_env_reset(uint8_t* obs, int32_t* state, int32_t* episode, int64_t N,
+                         int64_t env_offset, uint64_t seed, float* ep_ret, int32_t* ep_len,
+                         void* stream);
+int ppox_catch_env_step(const uint8_t* obs_in, uint8_t* obs_out, const int32_t* actions,
+                        int32_t* state, int32_t* episode, int64_t N, int64_t env_offset,
+                        uint64_t seed, float* rewards, uint8_t* dones, float* ep_ret,
+                        int32_t* ep_len, float* done_ret, int32_t* done_len, void* stream);
+
+/* ---------------------------------------------------------------------------
  * K6  NatureCNN convolutions (checkpoint models-checkpoint.py:52-58) and their
  * backward, as fp32 MFMA implicit GEMMs (v_mfma_f32_32x32x2_f32).
  *   layer 1: x = uint8 frames (batch, 4, 84, 84) [or rollout rows through idx:

@@ -11,31 +11,18 @@
 // .ipynb_checkpoints/env-checkpoint.py:16-17).  reward ~ Bernoulli(p_reward),
 // done ~ Bernoulli(p_done).  Traffic per env-step: 3 frames read + 4 written.
 #include "common.h"
+#include "episode.h"
 #include "philox.h"
 
 namespace {
+
+using ppox::Episode;
+using ppox::episode_update;
 
 constexpr int FRAME = 84 * 84;
 constexpr int CHUNKS = FRAME / 16;  // 441
 constexpr uint32_t EVENT_BLOCK = 0xFFFFFFFFu;
 constexpr uint32_t RESET_ACTION = 0xFFFFFFFFu;
-
-struct Episode {
-    float* ep_ret;
-    int32_t* ep_len;
-    float* done_ret;  // nullable: return of the episode that ended at this step, NaN otherwise
-    int32_t* done_len;
-};
-
-__device__ inline void episode_update(const Episode& ep, long long n, float rew, bool done) {
-    if (!ep.ep_ret) return;
-    const float r = ep.ep_ret[n] + rew;
-    const int l = ep.ep_len[n] + 1;
-    if (ep.done_ret) ep.done_ret[n] = done ? r : __builtin_nanf("");
-    if (ep.done_len) ep.done_len[n] = done ? l : 0;
-    ep.ep_ret[n] = done ? 0.f : r;
-    ep.ep_len[n] = done ? 0 : l;
-}
 
 __global__ void __launch_bounds__(256) atari_reset_kernel(uint8_t* __restrict__ obs, long long env_offset, uint32_t k0,
                                                           uint32_t k1, Episode ep) {

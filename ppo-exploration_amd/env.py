@@ -7,6 +7,10 @@ offline, and the reference's env processes are the one process boundary of
 its hot loop, so this build steps synthetic envs of the same observation/action
 shapes on the GPU (libppox ppox_atari_env_* / ppox_vec_env_*), sharded by
 global env index.  `make_env` keeps the reference's name and env_id argument.
+
+`make_env(..., dynamics="real")` is the opt-in alternative where the task itself is a
+few closed-form equations: the gym classic-control tasks (DeviceControlEnv) and Catch,
+a pixel task of the Atari shape (DeviceCatchEnv), stepped by csrc/env_real.hip.
 """
 import math
 
@@ -170,6 +174,109 @@ class DeviceVecEnv:
 DeviceAtariEnv.unnormalize_obs = DeviceVecEnv.unnormalize_obs
 
 
+# real dynamics: kernel kind, state dim, obs dim, action space, max episode length
+CONTROL_ENVS = {
+    "CartPole-v1": (native.CONTROL_CARTPOLE, 4, 4, Discrete(2), 500),
+    "CartPole-v0": (native.CONTROL_CARTPOLE, 4, 4, Discrete(2), 200),
+    "MountainCar-v0": (native.CONTROL_MOUNTAINCAR, 2, 2, Discrete(3), 200),
+    "Acrobot-v1": (native.CONTROL_ACROBOT, 4, 6, Discrete(3), 500),
+    "Pendulum-v1": (native.CONTROL_PENDULUM, 2, 3, Box((1,), -2.0, 2.0), 200),
+}
+REAL_ENVS = tuple(CONTROL_ENVS) + ("Catch-v0",)
+
+
+class DeviceControlEnv:
+    """A gym classic-control task stepped on the device (csrc/env_real.hip): CartPole-v1/-v0,
+    MountainCar-v0, Acrobot-v1, Pendulum-v1.  The equations are the published gym tasks restated
+    (DESIGN.md "Real-dynamics envs" is the specification); gym is not installed, so parity with
+    gym itself is unpinned — pinned is the numpy twin of the same equations (tests/real_env_twin.py).
+
+    The physics state (`state`, (N, S) float64) and the per-env episode index (`episode`, int32)
+    live here, not in the observation buffer, so the env steps under VecNormalize unchanged.
+    Reset draws are keyed by (global env id, episode index): sharding never changes the data.
+    Discrete kinds take the rollout's (N,) int32 actions, Pendulum its (N, 1) float32 ones."""
+
+    def __init__(self, env_id, n_envs, seed=0, env_offset=0, device="cuda", max_len=None):
+        if env_id not in CONTROL_ENVS:
+            raise ValueError(f"no real dynamics for {env_id!r}: supported ids are {', '.join(CONTROL_ENVS)}")
+        self.kind, s_dim, self.obs_dim, self.action_space, ml = CONTROL_ENVS[env_id]
+        self.env_id = env_id
+        self.num_envs = n_envs
+        self.env_offset = env_offset
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.max_len = ml if max_len is None else int(max_len)
+        if self.max_len < 1:
+            raise ValueError("max_len must be positive")
+        self.device = torch.device(device)
+        self.observation_space = Box((self.obs_dim,))
+        self.obs_dtype = torch.float32
+        self._act_dtype = torch.int32 if isinstance(self.action_space, Discrete) else torch.float32
+        self.state = torch.zeros((n_envs, s_dim), dtype=torch.float64, device=self.device)
+        self.episode = torch.zeros(n_envs, dtype=torch.int32, device=self.device)
+        self.ep_ret = torch.zeros(n_envs, device=self.device)
+        self.ep_len = torch.zeros(n_envs, dtype=torch.int32, device=self.device)
+        self._obs = None
+
+    def reset_into(self, obs):
+        native.control_env_reset(self.kind, self.state, self.episode, obs, self.num_envs, self.env_offset, self.seed,
+                                 self.ep_ret, self.ep_len)
+
+    def step_into(self, obs_in, obs_out, actions, rewards, dones, done_ret=None, done_len=None):
+        """obs_in is not read (the state is the env's own); obs_out may be the same buffer."""
+        if actions is None or actions.dtype != self._act_dtype or actions.numel() != self.num_envs:
+            raise TypeError(f"{self.env_id} takes {self.num_envs} {self._act_dtype} actions")
+        native.control_env_step(self.kind, self.state, self.episode, actions, obs_out, self.num_envs, self.env_offset,
+                                self.seed, self.max_len, rewards, dones, self.ep_ret, self.ep_len, done_ret, done_len)
+
+    def reset(self):
+        self._obs = torch.empty((self.num_envs, self.obs_dim), device=self.device)
+        self.reset_into(self._obs)
+        return self._obs
+
+    def step(self, actions):
+        a = torch.as_tensor(actions, device=self.device).to(self._act_dtype).reshape(-1).contiguous()
+        nxt = torch.empty_like(self._obs)
+        rew = torch.empty(self.num_envs, device=self.device)
+        done = torch.empty(self.num_envs, dtype=torch.uint8, device=self.device)
+        dret = torch.empty(self.num_envs, device=self.device)
+        dlen = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        self.step_into(self._obs, nxt, a, rew, done, dret, dlen)
+        self._obs = nxt
+        return nxt, rew, done.bool(), episode_infos(dret, dlen)
+
+    def unnormalize_obs(self, obs):
+        return obs
+
+
+class DeviceCatchEnv(DeviceAtariEnv):
+    """Catch, a pixel task of the Atari observation shape (csrc/env_real.hip): a ball falls down a
+    12 x 12 grid of 7 x 7-pixel cells, bouncing off the side walls, and the 3-cell paddle on the
+    bottom row (actions stay / left / right) has to be under it when it lands: reward +1 or -1 on
+    the 11th step of every episode, 0 before.  `state` is (N, 4) int32 = ball column, ball row,
+    ball dx, paddle column; `episode` the per-env episode index, the Philox counter of the reset
+    draw — the env has no host step counter, so step_into_dc ignores the counter it is handed."""
+
+    def __init__(self, env_id="Catch-v0", n_envs=4, seed=0, env_offset=0, device="cuda"):
+        super().__init__(env_id, n_envs, seed=seed, env_offset=env_offset, device=device)
+        self.action_space = Discrete(3)
+        self.state = torch.zeros((n_envs, 4), dtype=torch.int32, device=self.device)
+        self.episode = torch.zeros(n_envs, dtype=torch.int32, device=self.device)
+
+    def reset_into(self, obs):
+        native.catch_env_reset(obs, self.state, self.episode, self.num_envs, self.env_offset, self.seed, self.ep_ret,
+                               self.ep_len)
+        self.k = 0
+
+    def step_into(self, obs_in, obs_out, actions, rewards, dones, done_ret=None, done_len=None):
+        self.k += 1
+        native.catch_env_step(obs_in, obs_out, actions, self.state, self.episode, self.num_envs, self.env_offset,
+                              self.seed, rewards, dones, self.ep_ret, self.ep_len, done_ret, done_len)
+
+    def step_into_dc(self, obs_in, obs_out, actions, rewards, dones, done_ret, done_len, step_base, step_off):
+        native.catch_env_step(obs_in, obs_out, actions, self.state, self.episode, self.num_envs, self.env_offset,
+                              self.seed, rewards, dones, self.ep_ret, self.ep_len, done_ret, done_len)
+
+
 class VecNormalize:
     """env.py:10-11 wraps every env in stable_baselines3's VecNormalize(env,
     norm_reward=True).  SB3 is not vendored in the reference (README.md:19, unpinned;
@@ -240,7 +347,10 @@ class VecNormalize:
 
     def step(self, actions):
         a = torch.as_tensor(actions, device=self.device)
-        a = a.to(torch.int32).reshape(-1).contiguous() if self.action_space.__class__.__name__ == "Discrete" else None
+        if self.action_space.__class__.__name__ == "Discrete":
+            a = a.to(torch.int32).reshape(-1).contiguous()
+        else:  # Box actions: read by the real-dynamics envs, dropped by the synthetic one
+            a = a.to(torch.float32).reshape(self.num_envs, -1).contiguous()
         nxt = torch.empty_like(self.raw)
         rew = torch.empty(self.num_envs, device=self.device)
         done = torch.empty(self.num_envs, dtype=torch.uint8, device=self.device)
@@ -266,10 +376,23 @@ def episode_infos(done_ret, done_len):
     return [{"episode": {"r": float(r[i]), "l": int(ln[i])}} if not np.isnan(r[i]) else {} for i in range(len(r))]
 
 
-def make_env(env_id, n_envs=4, seed=0, env_offset=0, device="cuda", normalize=True, **kw):
+def make_env(env_id, n_envs=4, seed=0, env_offset=0, device="cuda", normalize=True, dynamics="synthetic", **kw):
     """env.py:7-12 counterpart: the synthetic device env for env_id; vector envs are wrapped
     in VecNormalize(norm_reward=True) as in env.py:11 (Atari envs, which the reference
-    builds in env-checkpoint.py without it, are not)."""
+    builds in env-checkpoint.py without it, are not).
+
+    dynamics="real" (opt-in) steps the task's own equations instead: DeviceControlEnv for the
+    classic-control ids, wrapped the same way, and DeviceCatchEnv for "Catch-v0"."""
+    if dynamics == "real":
+        if env_id == "Catch-v0":
+            return DeviceCatchEnv(env_id, n_envs, seed=seed, env_offset=env_offset, device=device, **kw)
+        if env_id not in CONTROL_ENVS:
+            raise ValueError(f"dynamics='real' is not available for {env_id!r}: "
+                             f"supported ids are {', '.join(REAL_ENVS)}")
+        env = DeviceControlEnv(env_id, n_envs, seed=seed, env_offset=env_offset, device=device, **kw)
+        return VecNormalize(env, norm_reward=True) if normalize else env
+    if dynamics != "synthetic":
+        raise ValueError(f"dynamics must be 'synthetic' or 'real', not {dynamics!r}")
     if is_atari(env_id):
         return DeviceAtariEnv(env_id, n_envs, seed=seed, env_offset=env_offset, device=device, **kw)
     env = DeviceVecEnv(env_id, n_envs, seed=seed, env_offset=env_offset, device=device, **kw)

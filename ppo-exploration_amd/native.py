@@ -113,6 +113,10 @@ SIGNATURES = {
     "ppox_vec_env_reset": [_vp, _i64, _i32, _i64, _u64, _vp, _vp, _vp],
     "ppox_vec_env_step": [_vp, _vp, _i64, _i32, _i64, _u64, _i64, _f32, _i32, _vp, _vp, _vp, _vp,
                           _vp, _vp, _vp],
+    "ppox_control_env_reset": [_i32, _vp, _vp, _vp, _i64, _i64, _u64, _vp, _vp, _vp],
+    "ppox_control_env_step": [_i32, _vp, _vp, _vp, _vp, _i64, _i64, _u64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ppox_catch_env_reset": [_vp, _vp, _vp, _i64, _i64, _u64, _vp, _vp, _vp],
+    "ppox_catch_env_step": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ppox_nature_fc_fwd_splitk": [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
     "ppox_icm_pack_w1": [_vp, _i64, _vp, _vp],
     "ppox_icm_encode": [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -493,6 +497,34 @@ def vec_env_reset(obs, N, D, env_offset, seed, ep_ret=None, ep_len=None, stream=
 def vec_env_step(obs, actions, N, D, env_offset, seed, step, p_done, max_len, rewards, dones, ep_ret=None,
                  ep_len=None, done_ret=None, done_len=None, stream=None):
     call("ppox_vec_env_step", _p(obs), _p(actions), N, D, env_offset, seed, step, float(p_done), int(max_len),
+         _p(rewards), _p(dones), _p(ep_ret), _p(ep_len), _p(done_ret), _p(done_len), stream_ptr(stream))
+
+
+# include/ppox.h PPOX_CONTROL_*
+CONTROL_CARTPOLE, CONTROL_MOUNTAINCAR, CONTROL_ACROBOT, CONTROL_PENDULUM = 0, 1, 2, 3
+
+
+def control_env_reset(kind, state, episode, obs, N, env_offset, seed, ep_ret, ep_len, stream=None):
+    call("ppox_control_env_reset", int(kind), _p(state), _p(episode), _p(obs), N, env_offset, seed, _p(ep_ret),
+         _p(ep_len), stream_ptr(stream))
+
+
+def control_env_step(kind, state, episode, actions, obs, N, env_offset, seed, max_len, rewards, dones, ep_ret, ep_len,
+                     done_ret=None, done_len=None, stream=None):
+    """actions: (N,) int32 for the Discrete kinds, (N,) float32 for Pendulum."""
+    call("ppox_control_env_step", int(kind), _p(state), _p(episode), _p(actions), _p(obs), N, env_offset, seed,
+         int(max_len), _p(rewards), _p(dones), _p(ep_ret), _p(ep_len), _p(done_ret), _p(done_len),
+         stream_ptr(stream))
+
+
+def catch_env_reset(obs, state, episode, N, env_offset, seed, ep_ret=None, ep_len=None, stream=None):
+    call("ppox_catch_env_reset", _p(obs), _p(state), _p(episode), N, env_offset, seed, _p(ep_ret), _p(ep_len),
+         stream_ptr(stream))
+
+
+def catch_env_step(obs_in, obs_out, actions, state, episode, N, env_offset, seed, rewards, dones, ep_ret=None,
+                   ep_len=None, done_ret=None, done_len=None, stream=None):
+    call("ppox_catch_env_step", _p(obs_in), _p(obs_out), _p(actions), _p(state), _p(episode), N, env_offset, seed,
          _p(rewards), _p(dones), _p(ep_ret), _p(ep_len), _p(done_ret), _p(done_len), stream_ptr(stream))
 
 

@@ -8,7 +8,8 @@
 
 Keyword arguments and defaults are the reference's; added keywords:
 n_envs (the reference hard-codes 4, ppo.py:52), seed, device, env (a device env
-object; default: the synthetic env for env_id), quiet.
+object; default: the synthetic env for env_id), quiet, dynamics ("synthetic";
+"real": the task's own equations, env.make_env — classic control and Catch-v0).
 
 Per iteration on each rank:
   collect: T x [net forward (rocBLAS + MFMA convs) -> ppox_categorical_sample ->
@@ -189,7 +190,7 @@ class BaseAlgorithm:
     """ppo.py:22-118."""
 
     def __init__(self, env_id, lr, nstep, batch_size, n_epochs, gamma, gae_lam, clip_range, ent_coef, vf_coef,
-                 max_grad_norm, n_envs=4, seed=0, device=None, env=None, quiet=False):
+                 max_grad_norm, n_envs=4, seed=0, device=None, env=None, quiet=False, dynamics="synthetic"):
         self.env_id = env_id
         self.dist = DistContext.current()
         self.device = torch.device(device or "cuda")
@@ -207,7 +208,8 @@ class BaseAlgorithm:
         self.env_offset, self.local_envs = shard_range(n_envs, self.dist.rank, self.dist.world)
         self.seed = seed
         self.env = env if env is not None else make_env(env_id, n_envs=self.local_envs, seed=seed,
-                                                        env_offset=self.env_offset, device=self.device)
+                                                        env_offset=self.env_offset, device=self.device,
+                                                        dynamics=dynamics)
         self.state_dim = self.env.observation_space.shape[0]
         self.action_converter = ActionConverter(self.env.action_space)
         self.discrete = self.action_converter.action_type == "Discrete"
@@ -526,12 +528,13 @@ class PPO(BaseAlgorithm):
 
     def __init__(self, *, env_id, lr=3e-4, nstep=128, batch_size=128, n_epochs=10, gamma=0.99, gae_lam=0.95,
                  clip_range=0.2, ent_coef=.01, vf_coef=1, max_grad_norm=0.2, hidden_size=128, sim_hash=False,
-                 sil=False, n_envs=4, seed=0, device=None, env=None, quiet=False):
+                 sil=False, n_envs=4, seed=0, device=None, env=None, quiet=False, dynamics="synthetic"):
         if sil:
             raise NotImplementedError("self-imitation (sil=True) is broken in the reference "
                                       "(sil_module.py:14 vs buffer.py:406) and out of scope")
         super().__init__(env_id, lr, nstep, batch_size, n_epochs, gamma, gae_lam, clip_range, ent_coef, vf_coef,
-                         max_grad_norm, n_envs=n_envs, seed=seed, device=device, env=env, quiet=quiet)
+                         max_grad_norm, n_envs=n_envs, seed=seed, device=device, env=env, quiet=quiet,
+                         dynamics=dynamics)
         self.policy = Policy(self.env, hidden_size)
         self.rollout = self._new_rollout(RolloutStorage, gae_lam=gae_lam, gamma=gamma, sim_hash=sim_hash)
         self.flat = FlatParams(self.policy.net, self.device)
@@ -674,9 +677,10 @@ class PPO_RND(BaseAlgorithm):
     def __init__(self, *, env_id, lr=3e-4, nstep=128, batch_size=128, n_epochs=10, gamma=0.99, int_gamma=0.99,
                  gae_lam=0.95, clip_range=0.2, ent_coef=.01, vf_coef=0.5, int_vf_coef=0.5, max_grad_norm=0.2,
                  hidden_size=128, int_hidden_size=128, int_lr=3e-4, rnd_start=1e+3, n_envs=4, seed=0, device=None,
-                 env=None, quiet=False):
+                 env=None, quiet=False, dynamics="synthetic"):
         super().__init__(env_id, lr, nstep, batch_size, n_epochs, gamma, gae_lam, clip_range, ent_coef, vf_coef,
-                         max_grad_norm, n_envs=n_envs, seed=seed, device=device, env=env, quiet=quiet)
+                         max_grad_norm, n_envs=n_envs, seed=seed, device=device, env=env, quiet=quiet,
+                         dynamics=dynamics)
         self.policy = Policy(self.env, hidden_size, intrinsic_model=True)
         self.image = _is_image(self.env.observation_space)
         self.rnd_features = 84 * 84 if self.image else self.state_dim
@@ -831,9 +835,10 @@ class PPO_ICM(BaseAlgorithm):
     def __init__(self, *, env_id, lr=3e-4, int_lr=3e-4, nstep=128, batch_size=128, n_epochs=10, gamma=0.99,
                  gae_lam=0.95, clip_range=0.2, ent_coef=.01, vf_coef=0.5, max_grad_norm=0.2, hidden_size=128,
                  int_hidden_size=32, int_rew_integration=0.05, beta=0.2, policy_weight=1, n_envs=4, seed=0,
-                 device=None, env=None, quiet=False):
+                 device=None, env=None, quiet=False, dynamics="synthetic"):
         super().__init__(env_id, lr, nstep, batch_size, n_epochs, gamma, gae_lam, clip_range, ent_coef, vf_coef,
-                         max_grad_norm, n_envs=n_envs, seed=seed, device=device, env=env, quiet=quiet)
+                         max_grad_norm, n_envs=n_envs, seed=seed, device=device, env=env, quiet=quiet,
+                         dynamics=dynamics)
         self.int_rew_integration = int_rew_integration
         self.policy = Policy(self.env, hidden_size)
         self.rollout = self._new_rollout(RolloutStorage, gae_lam=gae_lam)
