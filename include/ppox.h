@@ -182,6 +182,19 @@ int ppox_simhash_keys(const float* obs, int64_t N, int64_t D, int64_t obs_stride
                       const double* A, int32_t* keys, void* stream);
 int ppox_simhash_apply(const int32_t* keys_all, int64_t n_total, int64_t offset, int64_t n_local,
                        uint32_t* counts, double beta, float* rewards, void* stream);
+/* K8 on uint8 (pixel) observations: the same 16-bit keys from an int8 hash matrix, exact in
+ * integers (an extension, the reference has no usable image hash).
+ * matrix: A8[b * D + d] = popcount(w & 0xFFFF) - popcount(w >> 16), w = word d % 4 of
+ * philox4x32_10({d / 4, b, 0, 0xFFFFFFFE}, key = seed); rowsum[b] = sum_d A8[b, d].
+ * keys[n] bit b = (sum_d A8[b, d] * obs[n * obs_stride + d] > 0), obs bytes unsigned; int32
+ * sums, so 16 * 255 * D < 2^31.  Any N, D >= 1, obs_stride >= D (16-byte aligned rows with
+ * D % 16 == 0 take the MFMA kernel, the rest a plain one; the keys are the same).  acc: a
+ * workspace of ppox_simhash_keys_u8_workspace_bytes(N) bytes (no need to zero it). */
+int ppox_simhash_matrix_i8(int64_t D, uint64_t seed, int8_t* A8, int32_t* rowsum, void* stream);
+int64_t ppox_simhash_keys_u8_workspace_bytes(int64_t N);
+int ppox_simhash_keys_u8(const uint8_t* obs, int64_t N, int64_t D, int64_t obs_stride,
+                         const int8_t* A8, const int32_t* rowsum, int32_t* acc, int32_t* keys,
+                         void* stream);
 
 /* ---------------------------------------------------------------------------
  * K5  Minibatch gather (buffer.py:41-52, 256-267): dst[r] = rollout row of the

@@ -66,7 +66,7 @@ class RolloutStorage(BaseBuffer):
     _fields = ("observations", "actions", "old_values", "old_log_probs", "advantages", "returns")
 
     def __init__(self, buffer_size, n_envs, obs_space, action_space, gae_lam=0.95, gamma=0.99, sim_hash=False,
-                 device="cuda", obs_dtype=None, draw_hash_matrix=True):
+                 device="cuda", obs_dtype=None, draw_hash_matrix=True, hash_seed=0):
         super().__init__(buffer_size, obs_space, action_space, n_envs=n_envs)
         self.gae_lam = gae_lam
         self.gamma = gamma
@@ -80,11 +80,26 @@ class RolloutStorage(BaseBuffer):
         self.A = np.random.randn(16, self.obs_shape[0]) if draw_hash_matrix else None
         T, N, d = buffer_size, n_envs, self.device
         self.do_hash, self.beta = bool(sim_hash), 0.1                  # buffer.py:141-146
+        # uint8 observations of any rank hash through the int8 Philox matrix (an
+        # extension pinned to tests/simhash_px_twin.py, not to the reference); the draw above stays
+        self.hash_px = self.do_hash and obs_dtype == torch.uint8
         if self.do_hash:
-            if len(self.obs_shape) != 1 or self.A is None:
-                raise NotImplementedError("sim_hash needs vector observations (A = randn(16, obs_dim), "
-                                          "buffer.py:137); image observations are out of scope")
-            self.hash_A = torch.from_numpy(self.A).to(d)
+            if self.hash_px:
+                D = int(np.prod(self.obs_shape))
+                self.hash_seed = int(hash_seed) & 0xFFFFFFFFFFFFFFFF
+                self.hash_A8 = torch.empty((16, D), dtype=torch.int8, device=d)
+                self.hash_rowsum = torch.empty(16, dtype=torch.int32, device=d)
+                native.simhash_matrix_i8(D, self.hash_seed, self.hash_A8, self.hash_rowsum)
+                self.hash_workspace = torch.empty(native.simhash_keys_u8_workspace_bytes(N) // 4, dtype=torch.int32,
+                                                  device=d)
+                # this rollout's keys, row t written by the hash of obs_slots[t]
+                self.hash_keys = torch.zeros((T, N), dtype=torch.int32, device=d)
+            elif len(self.obs_shape) != 1 or self.A is None:
+                raise NotImplementedError("sim_hash supports float32 vector observations (A = randn(16, obs_dim), "
+                                          "buffer.py:137) and uint8 observations of any shape (int8 Philox hash "
+                                          f"matrix); got {obs_dtype} observations of shape {self.obs_shape}")
+            else:
+                self.hash_A = torch.from_numpy(self.A).to(d)
             # the count table (buffer.py:136) as one u32 counter per 16-bit key; outlives reset()
             self.count_table = torch.zeros(native.SIMHASH_KEYS, dtype=torch.int32, device=d)
         self.obs_slots = torch.zeros((T + 1, N) + self.obs_shape, dtype=obs_dtype, device=d)
@@ -131,22 +146,31 @@ class RolloutStorage(BaseBuffer):
             self.log_probs[t].copy_(_to_dev(log_prob, self.device).reshape(self.n_envs, self.action_dim))
         self.rewards[t].copy_(_to_dev(reward, self.device).reshape(self.n_envs))
         if self.do_hash:
-            self.sim_hash(self.obs_slots[t], self.rewards[t])
+            self.sim_hash(self.obs_slots[t], self.rewards[t], t)
         self.masks[t].copy_(_to_dev(mask, self.device).reshape(self.n_envs))
         self.values[t].copy_(_to_dev(value, self.device).reshape(self.n_envs))
         self.pos += 1
         if self.pos == self.buffer_size:
             self.full = True
 
-    def sim_hash(self, obs, rewards):
+    def sim_hash(self, obs, rewards, t=None):
         """buffer.py:188-200 on the device: count bonus added to `rewards` (this rank's
         (n_envs,) f32 row, mutated in place and returned).  Keys of all ranks are
-        gathered so the replicated count table advances exactly as in one process."""
+        gathered so the replicated count table advances exactly as in one process.
+        uint8 observations are hashed in place (no conversion, no allocation: graph-capturable
+        without a process group) and their keys kept in hash_keys[t] (t: the step, default pos)."""
         x = obs.reshape(self.n_envs, -1)
-        if x.dtype != torch.float32 or x.stride(-1) != 1:
-            x = x.float().contiguous()
-        keys = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
-        native.simhash_keys(x, self.n_envs, x.shape[1], x.stride(0), self.hash_A, keys)
+        if self.hash_px:
+            if x.dtype != torch.uint8 or x.stride(-1) != 1:
+                raise TypeError("sim_hash: this storage hashes uint8 observations with contiguous rows")
+            keys = self.hash_keys[self.pos if t is None else t]
+            native.simhash_keys_u8(x, self.n_envs, x.shape[1], x.stride(0), self.hash_A8, self.hash_rowsum,
+                                   self.hash_workspace, keys)
+        else:
+            if x.dtype != torch.float32 or x.stride(-1) != 1:
+                x = x.float().contiguous()
+            keys = torch.empty(self.n_envs, dtype=torch.int32, device=self.device)
+            native.simhash_keys(x, self.n_envs, x.shape[1], x.stride(0), self.hash_A, keys)
         ctx = DistContext.current()
         if ctx.enabled:
             keys_all, offset, total = ctx.all_gather_cat(keys, dim=0), ctx.rank * self.n_envs, \

@@ -59,6 +59,8 @@ SIGNATURES = {
     "ppox_normal_sample": [_vp, _vp, _i64, _i32, _i64, _u64, _i64, _vp, _vp, _vp],
     "ppox_simhash_keys": [_vp, _i64, _i64, _i64, _vp, _vp, _vp],
     "ppox_simhash_apply": [_vp, _i64, _i64, _i64, _vp, _f64, _vp, _vp],
+    "ppox_simhash_matrix_i8": [_i64, _u64, _vp, _vp, _vp],
+    "ppox_simhash_keys_u8": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
     "ppox_gather_rows": [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp],
     "ppox_grad_sumsq": [_vp, _i64, _vp, _vp],
     "ppox_adam_step": [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _f64, _f64, _f64, _f64, _i64, _vp, _vp],
@@ -149,7 +151,8 @@ _RESTYPES = {"ppox_version": ctypes.c_char_p, "ppox_last_error": ctypes.c_char_p
              "ppox_nature_fc_fwd_splitk_workspace_bytes": ctypes.c_int64, "ppox_amax_slots": ctypes.c_int32,
              "ppox_head_hidden_pack_elems": ctypes.c_int64, "ppox_head_hidden_wgrad_workspace_bytes": ctypes.c_int64,
              "ppox_head_hidden_fwd_splitk_workspace_bytes": ctypes.c_int64,
-             "ppox_nature_conv2_wgrad_planes_workspace_bytes": ctypes.c_int64}
+             "ppox_nature_conv2_wgrad_planes_workspace_bytes": ctypes.c_int64,
+             "ppox_simhash_keys_u8_workspace_bytes": ctypes.c_int64}
 _RESTYPE_ARGS = {"ppox_rms_u8_workspace_bytes": [_i64, _i64], "ppox_nature_wgrad_splits": [_i32, _i64],
                  "ppox_nature_wgrad_workspace_bytes": [_i32, _i64], "ppox_nature_split_pack_elems": [_i32],
                  "ppox_nature_wgrad_split_workspace_bytes": [_i32, _i64],
@@ -160,7 +163,8 @@ _RESTYPE_ARGS = {"ppox_rms_u8_workspace_bytes": [_i64, _i64], "ppox_nature_wgrad
                  "ppox_icm_partials_bytes": [_i64, _i32], "ppox_icm_g1_pack_elems": [_i64],
                  "ppox_nature_fc_fwd_splitk_workspace_bytes": [_i64], "ppox_head_hidden_wgrad_workspace_bytes": [_i64],
                  "ppox_head_hidden_fwd_splitk_workspace_bytes": [_i64],
-                 "ppox_nature_conv2_wgrad_planes_workspace_bytes": [_i64]}
+                 "ppox_nature_conv2_wgrad_planes_workspace_bytes": [_i64],
+                 "ppox_simhash_keys_u8_workspace_bytes": [_i64]}
 
 _lib = None
 
@@ -420,6 +424,23 @@ def simhash_keys(obs, N, D, stride, A, keys, stream=None):
 
 def simhash_apply(keys_all, n_total, offset, n_local, counts, beta, rewards, stream=None):
     call("ppox_simhash_apply", _p(keys_all), n_total, offset, n_local, _p(counts), float(beta), _p(rewards),
+         stream_ptr(stream))
+
+
+def simhash_matrix_i8(D, seed, A8, rowsum, stream=None):
+    """The int8 hash matrix of uint8 observations (16 x D, Philox of `seed`) and its row sums."""
+    call("ppox_simhash_matrix_i8", int(D), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(A8, torch.int8, 16 * D, "A8"),
+         ptr(rowsum, torch.int32, 16, "rowsum"), stream_ptr(stream))
+
+
+def simhash_keys_u8_workspace_bytes(N):
+    return int(load().ppox_simhash_keys_u8_workspace_bytes(int(N)))
+
+
+def simhash_keys_u8(obs, N, D, stride, A8, rowsum, workspace, keys, stream=None):
+    """keys (N,) int32 of uint8 rows `obs` (read in place); workspace: int32, at least
+    simhash_keys_u8_workspace_bytes(N) bytes."""
+    call("ppox_simhash_keys_u8", _p(obs), N, D, stride, _p(A8), _p(rowsum), _p(workspace), _p(keys),
          stream_ptr(stream))
 
 

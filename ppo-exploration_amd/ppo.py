@@ -536,7 +536,8 @@ class PPO(BaseAlgorithm):
                          max_grad_norm, n_envs=n_envs, seed=seed, device=device, env=env, quiet=quiet,
                          dynamics=dynamics)
         self.policy = Policy(self.env, hidden_size)
-        self.rollout = self._new_rollout(RolloutStorage, gae_lam=gae_lam, gamma=gamma, sim_hash=sim_hash)
+        self.rollout = self._new_rollout(RolloutStorage, gae_lam=gae_lam, gamma=gamma, sim_hash=sim_hash,
+                                         hash_seed=seed)
         self.flat = FlatParams(self.policy.net, self.device)
         self._attach_convs()
         self.optimizer = self.flat
@@ -549,9 +550,12 @@ class PPO(BaseAlgorithm):
         self._ctables = None
 
     def _collect_graph_ok(self):
+        # a hashing rollout is captured only for uint8 frames without a process group: the keys' all-gather
+        # stays on the eager path
+        ro = self.rollout
         return (self._collect_graph_enabled and isinstance(self.env, DeviceAtariEnv) and self.discrete
-                and not self.rollout.do_hash and getattr(self.policy.net, "conv_impl", None) is not None
-                and self.device.type == "cuda")
+                and (not ro.do_hash or (ro.hash_px and not self.dist.enabled))
+                and getattr(self.policy.net, "conv_impl", None) is not None and self.device.type == "cuda")
 
     def _collect_steps_eager(self):
         ro, net = self.rollout, self.policy.net
@@ -563,7 +567,7 @@ class PPO(BaseAlgorithm):
             self.env.step_into(ro.obs_slots[t], ro.obs_slots[t + 1], ro.actions[t], ro.rewards[t], ro.masks[t],
                                ro.done_ret[t], ro.done_len[t])
             if ro.do_hash:                                  # rollout.add -> sim_hash(last_obs), buffer.py:176
-                ro.sim_hash(ro.obs_slots[t], ro.rewards[t])
+                ro.sim_hash(ro.obs_slots[t], ro.rewards[t], t)
             self.num_timesteps += self.num_envs
 
     def _collect_step_dc(self, t):
@@ -579,6 +583,8 @@ class PPO(BaseAlgorithm):
             ro.values[t].copy_(v)
         self.env.step_into_dc(ro.obs_slots[t], ro.obs_slots[t + 1], ro.actions[t], ro.rewards[t], ro.masks[t],
                               ro.done_ret[t], ro.done_len[t], self._ctr[1:2], t + 1)
+        if ro.do_hash:  # keys -> apply on preallocated buffers, the eager loop's order
+            ro.sim_hash(ro.obs_slots[t], ro.rewards[t], t)
 
     def _collect_graphed(self):
         """ppo.py:174-194 as one hipGraph replay: the first collect runs eagerly (packing the
