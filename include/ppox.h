@@ -343,7 +343,9 @@ int ppox_nchw_to_nhwc_relu_grad(const float* grad, const float* act, int64_t bat
  * observations: f32(clip((x - mean) / sqrt(var + eps), -clip, clip)) in f64 (obs_rms
  * updated with ppox_rms_update_f32 first); rewards, in place: ret = ret * gamma + r,
  * ret_rms.update(ret) (float64 pairwise moments, Chan merge; skipped when update = 0),
- * r = clip(r / sqrt(ret_rms.var + eps), -clip, clip), ret[dones] = 0.  n <= 524288. */
+ * r = clip(r / sqrt(ret_rms.var + eps), -clip, clip), ret[dones] = 0.  n <= 524288, and
+ * refused (PPOX_EINVAL, checked before the pointers) when numpy's pairwise split of n
+ * has more than 4096 leaves: every n up to 523784 fits, most of the last 503 sizes do not. */
 int ppox_normalize_obs_f32_ex(const float* x, int64_t rows, int64_t cols, int64_t row_stride,
                               const double* mean, const double* var, double eps, double clip,
                               float* out, void* stream);

@@ -5,13 +5,19 @@
 // Q = sum x^2 are exact, so they are accumulated in parallel over row chunks
 // in any order (chunk partials to a caller workspace, reduced in a fixed order;
 // no atomics).  mean = S / n is then bit-identical to numpy's float64 mean;
-// var = (Q - 2 m S + n m^2) / n is the exact sum of squared deviations about
-// the rounded mean, within ~1e-15 relative of numpy's sequential float64 sum.
+// var = (n Q - S^2) / n^2 with the numerator formed exactly in 64-bit integers:
+// at most two roundings (the numerator's conversion when it exceeds 2^53, the
+// division) from the exact variance, whatever the column's spread.  numpy's
+// own float64 sum of squared deviations lies within rows * 2^-53 relative of
+// the same value, so the two agree to that, not bit for bit.  (Expanding the
+// square in float64, Q - 2 m S + n m^2, cancels catastrophically on the
+// near-constant columns that frames are made of: 2e-10 relative at 257 rows.)
 // f32 feature batches (MLP envs, D > 1): one lane per column, rows summed
 // sequentially in f32 — numpy's own order for an axis-0 reduction, so the batch
 // moments are bit-identical.  Scalar streams (int_rew_rms, (N,) f32): numpy's
 // pairwise float32 summation reproduced exactly (leaves of <= 128 elements with
-// 8 accumulators, combined in the recursion's order).
+// 8 accumulators, combined in the recursion's order, one tree per 8192-element
+// ufunc buffer and the trees' sums added in order).
 // The Chan merge into the float64 state follows util.py:30-44 op for op.
 #include <algorithm>
 
@@ -65,8 +71,11 @@ __global__ void __launch_bounds__(256) u8_finalize(const unsigned long long* __r
     }
     const double n = (double)rows;
     const double m = (double)S / n;
-    const double ssd = ((double)Q - 2.0 * m * (double)S) + n * m * m;
-    const double bvar = (ssd > 0 ? ssd : 0.0) / n;
+    // rows < 2^22 (nchunks < 65536): n Q < 2^22 * 2^22 * 2^16 = 2^60 and S^2 < (2^22 * 2^8)^2 = 2^60;
+    // n Q >= S^2 (Cauchy-Schwarz), with equality exactly for a constant column
+    const unsigned long long un = (unsigned long long)rows;
+    const unsigned long long num = un * Q - S * S;
+    const double bvar = (double)num / (n * n);
     if (bmean_out) bmean_out[c] = m;
     if (bvar_out) bvar_out[c] = bvar;
     if (mean && var) {
@@ -126,25 +135,34 @@ __device__ T pw_leaf(F get, int off, int n) {
     return res;
 }
 
-// Enumerate leaves (thread 0), sum them in parallel, combine in recursion order (thread 0).
+// numpy's reduction hands its pairwise routine at most one ufunc buffer (np.getbufsize(), 8192
+// elements by default) of a contiguous array at a time, and adds the chunks' sums to the
+// accumulator (which starts at 0) in order: above 8192 elements np.sum is NOT one pairwise tree.
+constexpr int NP_BUF = 8192;
+
+// Enumerate leaves (thread 0), sum them in parallel, combine in recursion order, chunk after
+// chunk (thread 0).
 template <typename T = float, typename F>
 __device__ T pairwise_sum_block(F get, int n, int* leaf_off, int* leaf_len, T* leaf_sum, int* nleaves_sh) {
     if (threadIdx.x == 0) {
         Frame st[40];
-        int sp = 0, nl = 0;
-        st[sp++] = Frame{0, n, 0};
-        while (sp) {
-            Frame f = st[--sp];
-            if (f.n <= PW_BLOCK) {
-                leaf_off[nl] = f.off;
-                leaf_len[nl] = f.n;
-                ++nl;
-                continue;
+        int nl = 0;
+        for (int c0 = 0; c0 < n; c0 += NP_BUF) {
+            int sp = 0;
+            st[sp++] = Frame{c0, min(NP_BUF, n - c0), 0};
+            while (sp) {
+                Frame f = st[--sp];
+                if (f.n <= PW_BLOCK) {
+                    leaf_off[nl] = f.off;
+                    leaf_len[nl] = f.n;
+                    ++nl;
+                    continue;
+                }
+                int n2 = f.n / 2;
+                n2 -= n2 % 8;
+                st[sp++] = Frame{f.off + n2, f.n - n2, 0};  // right pushed first -> left visited first
+                st[sp++] = Frame{f.off, n2, 0};
             }
-            int n2 = f.n / 2;
-            n2 -= n2 % 8;
-            st[sp++] = Frame{f.off + n2, f.n - n2, 0};  // right pushed first -> left visited first
-            st[sp++] = Frame{f.off, n2, 0};
         }
         *nleaves_sh = nl;
     }
@@ -154,33 +172,36 @@ __device__ T pairwise_sum_block(F get, int n, int* leaf_off, int* leaf_len, T* l
     __syncthreads();
     T result = 0;
     if (threadIdx.x == 0) {
-        // post-order combine with a value stack
         Frame st[40];
         T vs[40];
-        int sp = 0, vp = 0, k = 0;
-        st[sp++] = Frame{0, n, 0};
-        while (sp) {
-            Frame& f = st[sp - 1];
-            if (f.n <= PW_BLOCK) {
-                vs[vp++] = leaf_sum[k++];
-                --sp;
-                continue;
+        int k = 0;
+        for (int c0 = 0; c0 < n; c0 += NP_BUF) {
+            // post-order combine with a value stack
+            int sp = 0, vp = 0;
+            st[sp++] = Frame{c0, min(NP_BUF, n - c0), 0};
+            while (sp) {
+                Frame& f = st[sp - 1];
+                if (f.n <= PW_BLOCK) {
+                    vs[vp++] = leaf_sum[k++];
+                    --sp;
+                    continue;
+                }
+                int n2 = f.n / 2;
+                n2 -= n2 % 8;
+                if (f.state == 0) {
+                    f.state = 1;
+                    st[sp++] = Frame{f.off, n2, 0};
+                } else if (f.state == 1) {
+                    f.state = 2;
+                    st[sp++] = Frame{f.off + n2, f.n - n2, 0};
+                } else {
+                    const T b = vs[--vp], a = vs[--vp];
+                    vs[vp++] = a + b;
+                    --sp;
+                }
             }
-            int n2 = f.n / 2;
-            n2 -= n2 % 8;
-            if (f.state == 0) {
-                f.state = 1;
-                st[sp++] = Frame{f.off, n2, 0};
-            } else if (f.state == 1) {
-                f.state = 2;
-                st[sp++] = Frame{f.off + n2, f.n - n2, 0};
-            } else {
-                const T b = vs[--vp], a = vs[--vp];
-                vs[vp++] = a + b;
-                --sp;
-            }
+            result = result + vs[0];
         }
-        result = vs[0];
     }
     return result;  // valid in thread 0 only
 }
@@ -281,6 +302,28 @@ __global__ void __launch_bounds__(256) vecnorm_reward_kernel(float* __restrict__
     }
 }
 
+// Leaves that pairwise_sum_block enumerates for n elements: the same split on the host.  The
+// kernels' leaf arrays hold MAX_LEAVES entries, and the count is not n / PW_BLOCK rounded up:
+// n2 is rounded down to a multiple of 8, so the halves are uneven and one of them can split once
+// more than the other (a full chunk of 8192 has 64 leaves, one of 8191 has 65).
+int64_t pairwise_leaves(int64_t n) {
+    int64_t st[64], leaves = (n / NP_BUF) * (NP_BUF / PW_BLOCK);  // full chunks: a power of two splits evenly
+    int sp = 0;
+    if (n % NP_BUF) st[sp++] = n % NP_BUF;
+    while (sp) {
+        const int64_t k = st[--sp];
+        if (k <= PW_BLOCK) {
+            ++leaves;
+            continue;
+        }
+        int64_t n2 = k / 2;
+        n2 -= n2 % 8;
+        st[sp++] = k - n2;
+        st[sp++] = n2;
+    }
+    return leaves;
+}
+
 }  // namespace
 
 extern "C" int64_t ppox_rms_u8_workspace_bytes(int64_t rows, int64_t cols) {
@@ -311,7 +354,11 @@ extern "C" int ppox_rms_update_f32(const float* x, int64_t rows, int64_t cols, i
     PPOX_REQUIRE(rows > 0 && cols > 0 && row_stride >= cols, "ppox_rms_update_f32: bad sizes");
     hipStream_t s = ppox::as_stream(stream);
     if (cols == 1) {
-        // a single column is reduced by numpy along a contiguous axis: pairwise
+        // a single column is reduced by numpy along a contiguous axis: pairwise.
+        // rows <= 64 * MAX_LEAVES cannot overflow the leaf arrays: a block of k > PW_BLOCK elements
+        // splits into n2 >= 64 (k / 2 >= 64 is rounded down to a multiple of 8) and k - n2 >= 65, so
+        // every leaf of a split holds at least 64 elements; only a last chunk of <= PW_BLOCK elements is
+        // a smaller leaf, which makes at most rows / 64 + 1 leaves below the cap and 2048 at it
         PPOX_REQUIRE(row_stride == 1 && rows <= (int64_t)MAX_LEAVES * 64, "ppox_rms_update_f32: unsupported 1-col");
         scalar_rms_scale<<<1, 256, 0, s>>>(const_cast<float*>(x), (int)rows, mean, var, count, 0);
     } else {
@@ -323,6 +370,8 @@ extern "C" int ppox_rms_update_f32(const float* x, int64_t rows, int64_t cols, i
 extern "C" int ppox_rms_scale_int_rewards(float* int_rewards, int64_t n, double* mean, double* var, double count,
                                           void* stream) {
     PPOX_REQUIRE(int_rewards && mean && var, "ppox_rms_scale_int_rewards: null pointer");
+    // n <= 64 * MAX_LEAVES: every leaf of a split holds at least 64 elements (ppox_rms_update_f32), so the
+    // leaf arrays cannot overflow
     PPOX_REQUIRE(n > 0 && n <= (int64_t)MAX_LEAVES * 64, "ppox_rms_scale_int_rewards: n=%lld unsupported",
                  (long long)n);
     scalar_rms_scale<<<1, 256, 0, ppox::as_stream(stream)>>>(int_rewards, (int)n, mean, var, count, 1);
@@ -367,8 +416,13 @@ extern "C" int ppox_normalize_obs_f32_ex(const float* x, int64_t rows, int64_t c
 extern "C" int ppox_vecnorm_reward(float* rewards, const uint8_t* dones, double* ret, int64_t n, double gamma,
                                    double* mean, double* var, double count, double eps, double clip, int32_t update,
                                    void* stream) {
+    // the size first, so that it is refused whatever else is passed.  No n above MAX_LEAVES * PW_BLOCK fits
+    // (a leaf holds at most PW_BLOCK elements), and many sizes just below it do not either (a ragged last
+    // chunk can hold more than 64 leaves): the leaves are counted, not bounded
+    PPOX_REQUIRE(n <= (int64_t)MAX_LEAVES * PW_BLOCK && (n <= 0 || pairwise_leaves(n) <= MAX_LEAVES),
+                 "ppox_vecnorm_reward: n=%lld splits into more than %d pairwise leaves (one block)", (long long)n,
+                 MAX_LEAVES);
     PPOX_REQUIRE(rewards && ret && mean && var && n > 0, "ppox_vecnorm_reward: bad arguments");
-    PPOX_REQUIRE(n <= (int64_t)MAX_LEAVES * PW_BLOCK, "ppox_vecnorm_reward: too many envs for one block");
     vecnorm_reward_kernel<<<1, 256, 0, ppox::as_stream(stream)>>>(rewards, dones, ret, (int)n, gamma, mean, var, count,
                                                                   eps, clip, update);
     PPOX_LAUNCHED("ppox_vecnorm_reward");
