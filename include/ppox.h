@@ -690,6 +690,57 @@ int ppox_icm_int_reward(const float* phi_s, const float* phi_n, const int32_t* a
                         int32_t n_actions, const float* seg, float eta, float* rewards, float* int_rewards,
                         void* stream);
 
+/* ---------------------------------------------------------------------------
+ * K12  Self-imitation learning, PPO(sil=True) (sil_module.py, buffer.py:397-490; the
+ * definition is tests/sil_twin.py).
+ * Ring: S steps x N envs, slot (s, n) at s*N + n: obs (the env's dtype), actions i32, old
+ * log-probs f32, returns f32 (the reward until the slot's episode ends), dones u8, state u8
+ * (0 empty, 1 pending, 2 active).  Minibatch / leaf index: env-major i = n*S + s.
+ * Trees: sum and min, 2P f64 nodes each (P a power of two >= S*N), children of node k at
+ * 2k, 2k + 1, leaf i at P + i; an empty or pending leaf holds 0 (sum) / +inf (min).
+ * max_priority: one f64 (starts at 1.0); n_active: one i64.
+ * -------------------------------------------------------------------------*/
+/* SilModule.step (sil_module.py:23-30) for a whole rollout: the T steps of (actions, log_probs,
+ * rewards, dones) (T, N) into ring steps [head, head + T) mod S, state pending, leaves cleared;
+ * obs (nullable with ring_obs): T steps of obs_step_bytes each, one or two device copies. */
+int ppox_sil_append(const void* obs, int64_t obs_step_bytes, const int32_t* actions,
+                    const float* log_probs, const float* rewards, const uint8_t* dones, int64_t T,
+                    int64_t N, void* ring_obs, int32_t* ring_actions, float* ring_log_probs,
+                    float* ring_returns, uint8_t* ring_dones, uint8_t* ring_state, int64_t S,
+                    int64_t head, double* sum_tree, double* min_tree, int64_t P, void* stream);
+/* add_episode + discount_with_dones + buffer.add's priority (sil_module.py:40-55, 99-105,
+ * buffer.py:443-444): per env, from step `newest` backwards over its pending slots; from the
+ * first done on, R = done ? r : r + gamma * R in f64, stored f32, state active, both leaves
+ * pow(*max_priority, alpha).  Slots newer than the newest done stay pending. */
+int ppox_sil_returns(float* ring_returns, const uint8_t* ring_dones, uint8_t* ring_state, int64_t S,
+                     int64_t N, int64_t newest, double gamma, double alpha, const double* max_priority,
+                     double* sum_tree, double* min_tree, int64_t P, void* stream);
+/* Every internal node of both trees from its children, bottom-up (the state SegmentTree.__setitem__,
+ * util.py:149-159, keeps after any leaf writes), and *n_active = active slots of ring_state[slots]. */
+int ppox_sil_tree_rebuild(double* sum_tree, double* min_tree, int64_t P, const uint8_t* ring_state,
+                          int64_t slots, int64_t* n_active, void* stream);
+/* sample_proportional + the importance weights of get() (buffer.py:446-472, util.py:178-201):
+ * mass = u[b] * root, the descent of find_prefixsum_idx (never into a right child whose sum is 0);
+ * idx[b] env-major; weights[b] = (p/sum * n)^-beta / (p_min/sum * n)^-beta in f64, stored f32
+ * (ones when beta == 0).  u: (B,) f64 in [0, 1). */
+int ppox_sil_sample(const double* sum_tree, const double* min_tree, int64_t P, const int64_t* n_active,
+                    const double* u, int64_t B, double beta, int64_t* idx, float* weights, void* stream);
+/* The SIL loss and its gradient (sil_module.py:64-84 as corrected in DESIGN.md §4.4) over the B
+ * sampled rows: delta = R - V, a = clamp(delta, 0, 10), L = 0.1 (L_pol + ent_coef L_ent) + 0.01 L_val.
+ * Writes dL/dlogits (B, A), dL/dvalues (B,), priority[b] = a; loss_accum[0..2] += L, mean a, 1
+ * through partials (PPOX_LOSS_PARTIALS x 4 f64, fixed order). */
+int ppox_sil_loss(const float* logits, const float* values, int64_t B, int32_t A, const int64_t* idx,
+                  int64_t S, int64_t N, const int32_t* ring_actions, const float* ring_log_probs,
+                  const float* ring_returns, const float* weights, float clip, float ent_coef,
+                  float* dlogits, float* dvalues, float* priority, double* partials, double* loss_accum,
+                  void* stream);
+/* update_priorities (buffer.py:454-459): leaves of idx[b] = pow(max(priority[b], 1e-6), alpha) (the
+ * last occurrence of a repeated index wins), *max_priority raised to the largest clamped priority,
+ * the leaves' ancestors recomputed level by level.  One workgroup. */
+int ppox_sil_update_priorities(const int64_t* idx, const float* priority, int64_t B, double alpha,
+                               double* sum_tree, double* min_tree, int64_t P, double* max_priority,
+                               void* stream);
+
 /* Data-parallel exchange (world > 1; replaces the per-minibatch torch.distributed all-reduces around the
  * sharded update, ppo.py:241-244 — the reference is single-process).  The one exception to "never
  * allocates": ppox_dp_comm_init creates the RCCL communicator, a stream and two events.

@@ -1,5 +1,5 @@
 """Device-resident rollout storage with the reference's interface
-(reference: buffer.py:13-394 — RolloutStorage, IntrinsicStorage).
+(reference: buffer.py:13-490 — RolloutStorage, IntrinsicStorage, PrioritizedReplayBuffer).
 
 Layout in HBM, per rank (T = buffer_size, N = n_envs on this rank), STEP-MAJOR
 like the reference's (buffer_size, n_envs, ...) arrays:
@@ -15,6 +15,9 @@ numpy-RNG permutation (buffer.py:239), mapped to (t, n) inside the kernels —
 the rollout is never flattened or copied.  get() still yields the reference's
 RolloutSample namedtuple (field names and per-field shapes of buffer.py:261-267)
 for API compatibility.
+
+PrioritizedReplayBuffer (buffer.py:397-490, PPO(sil=True)) is a ring of S steps in the same
+step-major layout with two segment trees over its env-major index (csrc/sil.hip).
 """
 from collections import namedtuple
 
@@ -268,6 +271,87 @@ class IntrinsicStorage(RolloutStorage):
         return self.RolloutSample(g(self.observations, idx), acts, g(self.values, idx), g(self.int_values, idx), lps,
                                   g(self.advantages, idx).reshape(B, 1), g(self.int_advantages, idx).reshape(B, 1),
                                   g(self.returns, idx), g(self.int_returns, idx))
+
+
+class PrioritizedReplayBuffer(BaseBuffer):
+    """buffer.py:397-490 on the device, for self-imitation learning: a ring of
+    S steps x n_envs in the rollout's step-major layout, S = max(ceil(buffer_size / n_envs),
+    min_steps), with a sum and a min segment tree (f64, 2P nodes, P the power of two >= S * n_envs)
+    over the env-major slot index i = n * S + s.  A slot is empty, pending (its episode has not
+    ended: no return yet, not sampled) or active.  Whole rollouts are appended (append_rollout) in
+    time order; the reference adds an episode when it ends.
+
+    Memory: the ring holds S * n_envs observations of the env's dtype.  The default buffer_size
+    50,000 (ppo.py:164) is 1.4 GB of 4 x 84 x 84 uint8 frames at 4 envs; at 4,096 envs x 128 steps
+    SilModule's floor min_steps = 2 * nstep makes it 256 steps = 29.6 GB."""
+
+    def __init__(self, buffer_size, n_envs, obs_space, action_space, alpha=0.6, device="cuda", gamma=0.99,
+                 min_steps=1):
+        super().__init__(buffer_size, obs_space, action_space, n_envs=n_envs)
+        if action_space.__class__.__name__ != "Discrete":
+            raise NotImplementedError("PrioritizedReplayBuffer stores Discrete actions (self-imitation on a Box "
+                                      "action space is not implemented)")
+        self.alpha, self.gamma = float(alpha), float(gamma)
+        self.device = d = torch.device(device)
+        N = n_envs
+        self.n_steps = S = max(-(-int(buffer_size) // N), int(min_steps))
+        self.capacity = P = 1 << max(S * N - 1, 0).bit_length()
+        obs_dtype = torch.uint8 if getattr(obs_space, "dtype", None) is np.uint8 else torch.float32
+        self.observations = torch.zeros((S, N) + self.obs_shape, dtype=obs_dtype, device=d)
+        self.actions = torch.zeros((S, N), dtype=torch.int32, device=d)
+        self.log_probs = torch.zeros((S, N), device=d)
+        self.returns = torch.zeros((S, N), device=d)           # the reward until the slot's episode ends
+        self.dones = torch.zeros((S, N), dtype=torch.uint8, device=d)
+        self.state = torch.zeros((S, N), dtype=torch.uint8, device=d)
+        self.buffer_sum = torch.zeros(2 * P, dtype=torch.float64, device=d)
+        self.buffer_min = torch.full((2 * P,), float("inf"), dtype=torch.float64, device=d)
+        self.max_priority = torch.ones(1, dtype=torch.float64, device=d)
+        self.n_active = torch.zeros(1, dtype=torch.int64, device=d)
+        self.head = 0  # the ring step the next rollout starts at
+
+    def tensors(self):
+        """The ring's device arrays by role (what the ppox_sil_* kernels read and write)."""
+        return {"obs": self.observations, "actions": self.actions, "log_probs": self.log_probs,
+                "returns": self.returns, "dones": self.dones, "state": self.state,
+                "sum_tree": self.buffer_sum, "min_tree": self.buffer_min}
+
+    def __len__(self):
+        """Active slots (one device read)."""
+        return int(self.n_active.item())
+
+    def append_rollout(self, observations, actions, log_probs, rewards, dones):
+        """The rollout's T steps into the ring, then returns of the episodes that ended and both
+        trees (ppox_sil_append -> ppox_sil_returns -> ppox_sil_tree_rebuild)."""
+        T = actions.shape[0]
+        ring = self.tensors()
+        native.sil_append(observations, actions, log_probs, rewards, dones, ring, self.head)
+        self.head = (self.head + T) % self.n_steps
+        native.sil_returns(ring, (self.head - 1) % self.n_steps, self.gamma, self.alpha, self.max_priority)
+        native.sil_tree_rebuild(self.buffer_sum, self.buffer_min, self.state, self.n_active)
+
+    def _gather(self, x, idx):
+        """(S, N, ...) step-major -> rows for env-major indices idx (as RolloutStorage._gather)."""
+        row = x[0, 0].numel() * x.element_size()
+        out = torch.empty((idx.numel(),) + tuple(x.shape[2:]), dtype=x.dtype, device=self.device)
+        native.gather_rows(x, self.n_steps, self.n_envs, row, row, idx, idx.numel(), out)
+        return out
+
+    def sample(self, u, beta):
+        """buffer.py:446-472 for the uniforms u (host float64 array in [0, 1)): env-major indices
+        (device int64) and importance weights (device f32)."""
+        u = torch.from_numpy(np.ascontiguousarray(u, dtype=np.float64))
+        if self.device.type == "cuda":
+            u = u.pin_memory()
+        u = u.to(self.device, non_blocking=True)
+        idx = torch.empty(u.numel(), dtype=torch.int64, device=self.device)
+        weights = torch.empty(u.numel(), device=self.device)
+        native.sil_sample(self.buffer_sum, self.buffer_min, self.n_active, u, beta, idx, weights)
+        return idx, weights
+
+    def update_priorities(self, indexes, priorities):
+        """buffer.py:454-459 (device int64 indexes, device f32 priorities)."""
+        native.sil_update_priorities(indexes, priorities, self.alpha, self.buffer_sum, self.buffer_min,
+                                     self.max_priority)
 
 
 # north_star names (SURVEY.md API-name mismatch note)

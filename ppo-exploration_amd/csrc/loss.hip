@@ -20,16 +20,13 @@
 // log(clamp(p, eps, 1-eps)), min/max ties split the gradient in half, clamp
 // masks inclusive.
 #include "common.h"
+#include "categorical.h"
 #include "philox.h"
 
 namespace {
 
 constexpr int P = PPOX_LOSS_PARTIALS;
 constexpr int NS = 8;  // partial columns
-constexpr float F32_EPS = 1.1920928955078125e-07f;
-
-// index map: env-major flat i -> step-major element (t*N + n)
-__device__ inline long long elem(long long i, long long T, long long N) { return (i % T) * N + (i / T); }
 
 struct Minibatch {
     const float* logits;
@@ -51,53 +48,6 @@ struct Minibatch {
     float clip;
 };
 
-// ---- categorical head (models.py:62-64 via torch.distributions.Categorical) ----
-template <int MAXA>
-struct CatRow {
-    float p[MAXA], q[MAXA], c[MAXA], lp[MAXA];
-    float s;  // sum of p (renormaliser)
-    float ent;
-};
-
-template <int MAXA>
-__device__ inline void categorical_forward(const float* zp, int A, CatRow<MAXA>& r) {
-    // the row's logits loaded unconditionally first (j >= A re-reads logit A - 1, never used):
-    // a load under the j < A branches below would cost a memory round trip per logit
-    float z[MAXA];
-#pragma unroll
-    for (int j = 0; j < MAXA; ++j) z[j] = zp[j < A ? j : A - 1];
-    float m = z[0];
-#pragma unroll
-    for (int j = 1; j < MAXA; ++j)
-        if (j < A) m = fmaxf(m, z[j]);
-    float S = 0.f;
-#pragma unroll
-    for (int j = 0; j < MAXA; ++j)
-        if (j < A) {
-            r.p[j] = expf(z[j] - m);
-            S += r.p[j];
-        }
-    const float inv = 1.0f / S;
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < MAXA; ++j)
-        if (j < A) {
-            r.p[j] = r.p[j] * inv;
-            s += r.p[j];
-        }
-    r.s = s;
-    float ent = 0.f;
-#pragma unroll
-    for (int j = 0; j < MAXA; ++j)
-        if (j < A) {
-            r.q[j] = r.p[j] / s;
-            r.c[j] = fminf(fmaxf(r.q[j], F32_EPS), 1.0f - F32_EPS);
-            r.lp[j] = logf(r.c[j]);
-            ent += r.lp[j] * r.q[j];
-        }
-    r.ent = -ent;
-}
-
 struct Scalars {
     float mean, std, imean, istd;
 };
@@ -112,8 +62,6 @@ __device__ inline Scalars load_stats(const double* st, bool dual) {
 }
 
 __device__ inline float norm_adv(float a, float mean, float std) { return (a - mean) / (std + 1e-8f); }
-
-__device__ inline float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 
 // ---------------------------------------------------------------------------
 template <int MAXA, bool DUAL>
@@ -593,24 +541,6 @@ __global__ void __launch_bounds__(256) normal_sample_kernel(const float* __restr
         }
     }
 }
-
-#define PPOX_DISPATCH_A(A, MAXA_NAME, ...)      \
-    if ((A) <= 4) {                             \
-        constexpr int MAXA_NAME = 4;            \
-        __VA_ARGS__;                            \
-    } else if ((A) <= 8) {                      \
-        constexpr int MAXA_NAME = 8;            \
-        __VA_ARGS__;                            \
-    } else if ((A) <= 18) {                     \
-        constexpr int MAXA_NAME = 18;           \
-        __VA_ARGS__;                            \
-    } else if ((A) <= 32) {                     \
-        constexpr int MAXA_NAME = 32;           \
-        __VA_ARGS__;                            \
-    } else {                                    \
-        constexpr int MAXA_NAME = 64;           \
-        __VA_ARGS__;                            \
-    }
 
 int check_mb(const Minibatch& m, bool dual, const char* name) {
     PPOX_REQUIRE(m.A >= 1 && m.A <= 64, "%s: n_actions=%d outside [1,64]", name, m.A);

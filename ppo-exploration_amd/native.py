@@ -128,6 +128,14 @@ SIGNATURES = {
     "ppox_icm_grad_reduce": [_vp, _i64, _i64, _i32, _f32, _i64, _vp, _vp, _vp],
     "ppox_icm_enc_wgrad": [_vp, _vp, _i64, _i64, _vp, _vp, _vp],
     "ppox_icm_int_reward": [_vp, _vp, _vp, _i64, _i32, _vp, _f32, _vp, _vp, _vp],
+    "ppox_sil_append": [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp,
+                        _i64, _vp],
+    "ppox_sil_returns": [_vp, _vp, _vp, _i64, _i64, _i64, _f64, _f64, _vp, _vp, _vp, _i64, _vp],
+    "ppox_sil_tree_rebuild": [_vp, _vp, _i64, _vp, _i64, _vp, _vp],
+    "ppox_sil_sample": [_vp, _vp, _i64, _vp, _vp, _i64, _f64, _vp, _vp, _vp],
+    "ppox_sil_loss": [_vp, _vp, _i64, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp,
+                      _vp],
+    "ppox_sil_update_priorities": [_vp, _vp, _i64, _f64, _vp, _vp, _i64, _vp, _vp],
     "ppox_dp_load": [ctypes.c_char_p],
     "ppox_event_create": [ctypes.c_uint32, ctypes.POINTER(_vp)],
     "ppox_event_destroy": [_vp],
@@ -1048,6 +1056,88 @@ def icm_int_reward(phi_s, phi_n, actions, N, n_actions, seg, eta, rewards, int_r
     call("ppox_icm_int_reward", _p(phi_s), _p(phi_n), ptr(actions, torch.int32, name="actions"), int(N),
          int(n_actions), _p(seg), float(eta), ptr(rewards, torch.float32, name="rewards"),
          ptr(int_rewards, torch.float32, name="int_rewards"), stream_ptr(stream))
+
+
+# ---------------------------------------------------------------------------
+# K12 self-imitation learning: prioritized replay ring, segment trees, loss (csrc/sil.hip)
+# ---------------------------------------------------------------------------
+SIL_EMPTY, SIL_PENDING, SIL_ACTIVE = 0, 1, 2  # the ring's state byte (include/ppox.h K12)
+
+
+def sil_append(obs, actions, log_probs, rewards, dones, ring, head, stream=None):
+    """The rollout's T steps ((T, N) actions i32, log_probs, rewards f32, dones u8; obs (T, N, ...) or
+    None) into ring steps [head, head + T) mod S.  ring: dict of the ring's tensors (obs or None,
+    actions, log_probs, returns, dones, state (S, N); sum_tree, min_tree (2P,) f64)."""
+    T, N = actions.shape
+    S = ring["state"].shape[0]
+    f32, u8, i32, f64 = torch.float32, torch.uint8, torch.int32, torch.float64
+    P = ring["sum_tree"].numel() // 2
+    robs = ring.get("obs")
+    if (obs is None) != (robs is None):
+        raise ValueError("sil_append: obs and the ring's obs must both be given or both be None")
+    step_bytes = 0
+    if obs is not None:
+        if obs.dtype != robs.dtype or obs.shape[1:] != robs.shape[1:] or obs.shape[0] != T:
+            raise ValueError(f"sil_append: obs {tuple(obs.shape)} {obs.dtype} does not match the ring's "
+                             f"{tuple(robs.shape)} {robs.dtype}")
+        step_bytes = obs[0].numel() * obs.element_size()
+    call("ppox_sil_append", ptr(obs, name="obs"), step_bytes, ptr(actions, i32, T * N, "actions"),
+         ptr(log_probs, f32, T * N, "log_probs"), ptr(rewards, f32, T * N, "rewards"), ptr(dones, u8, T * N, "dones"),
+         T, N, ptr(robs, name="ring obs"), ptr(ring["actions"], i32, S * N, "ring actions"),
+         ptr(ring["log_probs"], f32, S * N, "ring log_probs"), ptr(ring["returns"], f32, S * N, "ring returns"),
+         ptr(ring["dones"], u8, S * N, "ring dones"), ptr(ring["state"], u8, S * N, "ring state"), S, int(head),
+         ptr(ring["sum_tree"], f64, 2 * P, "sum_tree"), ptr(ring["min_tree"], f64, 2 * P, "min_tree"), P,
+         stream_ptr(stream))
+
+
+def sil_returns(ring, newest, gamma, alpha, max_priority, stream=None):
+    S, N = ring["state"].shape
+    f32, u8, f64 = torch.float32, torch.uint8, torch.float64
+    P = ring["sum_tree"].numel() // 2
+    call("ppox_sil_returns", ptr(ring["returns"], f32, S * N, "ring returns"), ptr(ring["dones"], u8, S * N, "ring dones"),
+         ptr(ring["state"], u8, S * N, "ring state"), S, N, int(newest), float(gamma), float(alpha),
+         ptr(max_priority, f64, 1, "max_priority"), ptr(ring["sum_tree"], f64, 2 * P, "sum_tree"),
+         ptr(ring["min_tree"], f64, 2 * P, "min_tree"), P, stream_ptr(stream))
+
+
+def sil_tree_rebuild(sum_tree, min_tree, state, n_active, stream=None):
+    """state: the ring's state bytes (or None: no slots, n_active = 0)."""
+    P = sum_tree.numel() // 2
+    f64 = torch.float64
+    call("ppox_sil_tree_rebuild", ptr(sum_tree, f64, 2 * P, "sum_tree"), ptr(min_tree, f64, 2 * P, "min_tree"), P,
+         ptr(state, torch.uint8, name="ring state"), 0 if state is None else state.numel(),
+         ptr(n_active, torch.int64, 1, "n_active"), stream_ptr(stream))
+
+
+def sil_sample(sum_tree, min_tree, n_active, u, beta, idx, weights, stream=None):
+    P = sum_tree.numel() // 2
+    B = u.numel()
+    f64 = torch.float64
+    call("ppox_sil_sample", ptr(sum_tree, f64, 2 * P, "sum_tree"), ptr(min_tree, f64, 2 * P, "min_tree"), P,
+         ptr(n_active, torch.int64, 1, "n_active"), ptr(u, f64, B, "u"), B, float(beta),
+         ptr(idx, torch.int64, B, "idx"), ptr(weights, torch.float32, B, "weights"), stream_ptr(stream))
+
+
+def sil_loss(logits, values, idx, ring, weights, clip, ent_coef, dlogits, dvalues, priority, partials, loss_accum,
+             stream=None):
+    B, A = logits.shape
+    S, N = ring["state"].shape
+    f32 = torch.float32
+    call("ppox_sil_loss", ptr(logits, f32, B * A, "logits"), ptr(values, f32, B, "values"), B, A,
+         ptr(idx, torch.int64, B, "idx"), S, N, _p(ring["actions"]), _p(ring["log_probs"]), _p(ring["returns"]),
+         ptr(weights, f32, B, "weights"), float(clip), float(ent_coef), ptr(dlogits, f32, B * A, "dlogits"),
+         ptr(dvalues, f32, B, "dvalues"), ptr(priority, f32, B, "priority"),
+         ptr(partials, torch.float64, LOSS_PARTIALS * 4, "partials"), ptr(loss_accum, torch.float64, name="loss_accum"),
+         stream_ptr(stream))
+
+
+def sil_update_priorities(idx, priority, alpha, sum_tree, min_tree, max_priority, stream=None):
+    P = sum_tree.numel() // 2
+    B = idx.numel()
+    f64 = torch.float64
+    call("ppox_sil_update_priorities", ptr(idx, torch.int64, B, "idx"), ptr(priority, torch.float32, B, "priority"), B,
+         float(alpha), ptr(sum_tree, f64, 2 * P, "sum_tree"), ptr(min_tree, f64, 2 * P, "min_tree"), P,
+         ptr(max_priority, f64, 1, "max_priority"), stream_ptr(stream))
 
 
 # ---------------------------------------------------------------------------

@@ -9,7 +9,8 @@
 Keyword arguments and defaults are the reference's; added keywords:
 n_envs (the reference hard-codes 4, ppo.py:52), seed, device, env (a device env
 object; default: the synthetic env for env_id), quiet, dynamics ("synthetic";
-"real": the task's own equations, env.make_env — classic control and Catch-v0).
+"real": the task's own equations, env.make_env — classic control and Catch-v0), sil_kwargs (PPO(sil=True):
+size, alpha, beta, epochs, batch of the self-imitation module, sil_module.py).
 
 Per iteration on each rank:
   collect: T x [net forward (rocBLAS + MFMA convs) -> ppox_categorical_sample ->
@@ -37,6 +38,7 @@ from buffer import IntrinsicStorage, RolloutStorage
 from dist import DistContext, owned_minibatch_indices, owned_minibatch_positions, shard_range
 from env import DeviceAtariEnv, make_env
 from phases import traced
+from sil_module import SilModule
 from models import CnnActorCritic, FlatParams, IntrinsicCuriosityModule, MlpNetwork, RndNetwork
 from util import ActionConverter, RunningMeanStd
 
@@ -528,10 +530,14 @@ class PPO(BaseAlgorithm):
 
     def __init__(self, *, env_id, lr=3e-4, nstep=128, batch_size=128, n_epochs=10, gamma=0.99, gae_lam=0.95,
                  clip_range=0.2, ent_coef=.01, vf_coef=1, max_grad_norm=0.2, hidden_size=128, sim_hash=False,
-                 sil=False, n_envs=4, seed=0, device=None, env=None, quiet=False, dynamics="synthetic"):
-        if sil:
-            raise NotImplementedError("self-imitation (sil=True) is broken in the reference "
-                                      "(sil_module.py:14 vs buffer.py:406) and out of scope")
+                 sil=False, n_envs=4, seed=0, device=None, env=None, quiet=False, dynamics="synthetic",
+                 sil_kwargs=None):
+        if sil and sim_hash:
+            raise NotImplementedError("sil=True with sim_hash=True: the count bonus is written into the rollout's "
+                                      "rewards, which self-imitation would replay as returns")
+        if sil and DistContext.current().enabled:
+            raise NotImplementedError("sil=True under a process group: the replay ring and its priority trees are "
+                                      "not sharded over ranks")
         super().__init__(env_id, lr, nstep, batch_size, n_epochs, gamma, gae_lam, clip_range, ent_coef, vf_coef,
                          max_grad_norm, n_envs=n_envs, seed=seed, device=device, env=env, quiet=quiet,
                          dynamics=dynamics)
@@ -542,12 +548,28 @@ class PPO(BaseAlgorithm):
         self._attach_convs()
         self.optimizer = self.flat
         self.sim_hash, self.sil = sim_hash, sil
+        self.sil_module = None
+        if sil:
+            self._init_sil(dict(sil_kwargs or {}), gamma)
         self._alloc_train_state()
         self.last_obs = None
         # the collect step loop as one captured graph (PPOX_COLLECT_GRAPH=0: eager launches)
         self._collect_graph_enabled = native.ab_env("PPOX_COLLECT_GRAPH", "1") != "0"
         self._cgraph = None
         self._ctables = None
+
+    def _init_sil(self, kw, gamma):
+        """ppo.py:163-164, 252: SilModule(50000, ...) trained for 4 epochs of 128 rows; sil_kwargs
+        overrides size, alpha, beta, epochs, batch."""
+        if not self.discrete:
+            raise NotImplementedError("sil=True needs a Discrete action space (the self-imitation loss kernel has "
+                                      "the Categorical head only)")
+        self._sil_epochs, self._sil_batch = int(kw.pop("epochs", 4)), int(kw.pop("batch", 128))
+        size, alpha, beta = kw.pop("size", 50000), kw.pop("alpha", 0.6), kw.pop("beta", 1.0)
+        if kw:
+            raise TypeError(f"sil_kwargs: unknown keys {sorted(kw)} (size, alpha, beta, epochs, batch)")
+        self.sil_module = SilModule(size, self.policy, self.optimizer, self.local_envs, self.env, gamma=gamma,
+                                    nstep=self.nstep, alpha=alpha, beta=beta, device=self.device, algo=self)
 
     def _collect_graph_ok(self):
         # a hashing rollout is captured only for uint8 frames without a process group: the keys' all-gather
@@ -625,6 +647,8 @@ class PPO(BaseAlgorithm):
         ro.pos, ro.full = self.nstep, True
         # ppo.py:196 bootstraps with V(s_{T-1}) and the last step's dones
         ro.compute_returns_and_advantages(ro.values[self.nstep - 1], ro.masks[self.nstep - 1])
+        if self.sil_module is not None:                                        # ppo.py:189-190, per rollout
+            self.sil_module.step_rollout(ro)
         self._finish_episodes()
         self.last_obs = ro.obs_slots[self.nstep]
         return True
@@ -668,6 +692,8 @@ class PPO(BaseAlgorithm):
                 idx = local[offs[k]:offs[k + 1]]
                 self._minibatch(idx, stats[k], B)
                 self.flat.adam_step(self.lr, self.max_grad_norm)
+        if self.sil_module is not None:                                        # ppo.py:251-252
+            self.sil_module.train(self._sil_epochs, self._sil_batch, clip_range=0.2)
         self._record_train()
         self._n_updates += self.n_epochs
 
