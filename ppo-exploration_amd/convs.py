@@ -32,37 +32,30 @@ SPLIT_OPS = {("fwd", 1), ("fwd", 2), ("fwd", 3), ("dgrad", 2), ("dgrad", 3), ("w
 # with its col2im-form kernel (dgrad2_col_kernel: 0.68 vs 0.97 ms f32 at B = 16384, 0.091 vs
 # 0.136 ms at the 8-GPU per-rank minibatch of 2048)
 SPLIT_SLOWER = set()
-# fc forward: the split-f16 GEMM from FC_SPLIT_MIN_BATCH up (rocBLAS below; PPOX_FC_SPLIT_MIN
-# overrides, default: every batch), split over K below FC_SPLITK_MAX_BATCH (tools/fc_bench.py,
+# fc forward: the split-f16 GEMM from FC_SPLIT_MIN_BATCH up (rocBLAS below; every batch, tests
+# patch it), split over K below FC_SPLITK_MAX_BATCH (tools/fc_bench.py,
 # r02: split-K 0.018 / 0.045 / 0.078 ms vs rocBLAS 0.026 / 0.062 / 0.119 ms at 512 / 2048 /
 # 4096 rows; the plain split GEMM 0.146 vs split-K 0.152 ms at 8192)
-FC_SPLIT_MIN_BATCH = int(native.ab_env("PPOX_FC_SPLIT_MIN", "0"))
-FC_SPLITK_MAX_BATCH = int(native.ab_env("PPOX_FC_SPLITK_MAX", "8192"))
-# fc dgrad fused with the trunk's ReLU backward + NHWC transpose (split-f16) up to this
-# batch (PPOX_FC_DGRAD_FUSED_MAX overrides): faster than rocBLAS + nchw_to_nhwc_mask at
-# every measured batch (A/B: -33 ms per iteration at 16384, -2 ms at 2048)
-FC_DGRAD_FUSED_MAX_BATCH = int(native.ab_env("PPOX_FC_DGRAD_FUSED_MAX", str(1 << 62)))
-# fc weight gradient on the split wgrad kernel (ppox_nature_fc_wgrad) from this batch up,
-# the rocBLAS f32 GEMM + NHWC -> Flatten permute below (PPOX_FC_WGRAD_SPLIT_MIN overrides)
-FC_WGRAD_SPLIT_MIN_BATCH = int(native.ab_env("PPOX_FC_WGRAD_SPLIT_MIN", "0"))
+FC_SPLIT_MIN_BATCH = 0
+FC_SPLITK_MAX_BATCH = 8192
+# In split math the fc dgrad is the split-f16 kernel fused with the trunk's ReLU backward + NHWC
+# transpose at every batch: faster than rocBLAS + nchw_to_nhwc_mask at every measured batch (A/B:
+# -33 ms per iteration at 16384, -2 ms at 2048); the fc weight gradient is the split wgrad kernel
+# (ppox_nature_fc_wgrad) at every batch.
 
 # the heads' hidden layer Linear(512, 512) on the split-f16 GEMM (ppox_head_hidden_*) from this
-# batch up, rocBLAS f32 below (PPOX_HEAD_SPLIT_MIN overrides)
-HEAD_SPLIT_MIN_BATCH = int(native.ab_env("PPOX_HEAD_SPLIT_MIN", "8192"))
+# batch up, rocBLAS f32 below.  (This gate and the two after it are patched by tests: the C4 test's
+# rounding-only control runs the hidden layer on the library GEMMs throughout.)
+HEAD_SPLIT_MIN_BATCH = 8192
 # below HEAD_SPLIT_MIN_BATCH the hidden layer's forward still runs on the split-f16 kernel, split over K
-# with the critic head fused into its reduce (its backward stays on the library GEMMs);
-# PPOX_HEAD_FWD_SPLITK=0 keeps the library GEMM
-HEAD_FWD_SPLITK = native.ab_env("PPOX_HEAD_FWD_SPLITK", "1") == "1"
+# with the critic head fused into its reduce; False keeps the library GEMM
+HEAD_FWD_SPLITK = True
 # the hidden layer's backward (dgrad into the fc layer's input grad + weight gradient) on the split-f16
-# kernels from this batch up, the library GEMMs below (PPOX_HEAD_BWD_SPLIT_MIN).  Round 4: at every batch —
-# the same GPU time at the per-rank 2,048 rows (same-box A/B 199.57 vs 199.55-199.79 ms per iteration,
-# profiles/r04_ab.txt) and no library GEMM on the host's launch path (the two rocBLAS calls cost ~100 us of
-# host time per minibatch, which the 8-rank path spends on its collectives)
-HEAD_BWD_SPLIT_MIN_BATCH = int(native.ab_env("PPOX_HEAD_BWD_SPLIT_MIN", "0"))
-
-# ReLU masks of the conv outputs as bitmasks written by the split forwards for the split dgrads
-# (PPOX_RELU_BITS=0: the dgrads read the f32 activations)
-RELU_BITS = native.ab_env("PPOX_RELU_BITS", "1") != "0"
+# kernels from this batch up, the library GEMMs below.  Round 4: at every batch — the same GPU time at
+# the per-rank 2,048 rows (same-box A/B 199.57 vs 199.55-199.79 ms per iteration, profiles/r04_ab.txt)
+# and no library GEMM on the host's launch path (the two rocBLAS calls cost ~100 us of host time per
+# minibatch, which the 8-rank path spends on its collectives)
+HEAD_BWD_SPLIT_MIN_BATCH = 0
 
 # rows of a pass's amax table (native.amax_table): the split-f16 operands of the trunk and the
 # heads' hidden layer, each recorded by the kernel that produces it and read by its consumers;
@@ -75,20 +68,22 @@ EX_H2, EX_H3, EX_G3, EX_DF, EX_G2 = range(5)
 # two f16 planes too — h2 (written by the conv2 forward, read by the conv3 forward and weight
 # gradient), h3 (conv3 forward -> fc forward and fc weight gradient) and g3 (fc dgrad -> conv3
 # dgrad and weight gradient) — at exponents derived from bounds, so no consumer splits in
-# registers.  PPOX_PX=0: f32 tensors (split in the consumers).  Needs the ReLU bitmasks (the
-# dgrads' masks cannot come from planes).
-PX = native.ab_env("PPOX_PX", "1") != "0"
-# ... from this batch up (PPOX_PX_MIN): every batch since the direct conv2 / conv3 forwards (csrc/dconv.hip,
-# which need the planes; same-box A/B: 1-GPU line 478.6k vs 469.9k env-steps/s — the collect forward at 4,096
-# rows gains most — and per-rank 204.8 vs 207.3 ms; before them PX at 2,048 rows measured 225.8 vs 219.5 ms)
-PX_MIN_BATCH = int(native.ab_env("PPOX_PX_MIN", "0"))
-# PX df (round 4, PPOX_PX_DF=1): the fc layer's df (B x 512, its amax recorded by the head backward)
-# split into its planes by one small kernel (ppox_px_split) for the fc dgrad and weight gradient, which
-# otherwise split every df value in registers once per tile (the fc dgrad: 49 times).  On by default
-# since the direct fc dgrad (csrc/dconv.hip fcd_kernel, which reads the planes: 195 vs 277 us at 16,384
-# rows); with the sg2 fc dgrad alone it measured neutral-to-slower (profiles/r04_ab.txt: 1-GPU 1,152.5
-# vs 1,146.8 ms, per-rank 203.9 vs 201.8 ms per iteration)
-PX_DF = native.ab_env("PPOX_PX_DF", "1") == "1"
+# registers (the dgrads' masks come from the ReLU bitmasks: they cannot come from planes).  At every
+# batch since the direct conv2 / conv3 forwards (csrc/dconv.hip, which need the planes; same-box A/B:
+# 1-GPU line 478.6k vs 469.9k env-steps/s — the collect forward at 4,096 rows gains most — and per-rank
+# 204.8 vs 207.3 ms; before them PX at 2,048 rows measured 225.8 vs 219.5 ms).  Tests turn it off: for
+# the trunks built while PX is False (the C4 test's control), per trunk (NatureConvs.px) or per pass
+# (forward_acts' px=); the consumers then split f32 tensors in registers.
+PX = True
+# ... from this batch up: every batch (tests patch it by name)
+PX_MIN_BATCH = 0
+# PX df (round 4): the fc layer's df (B x 512, its amax recorded by the head backward) split into its
+# planes once for the fc dgrad and weight gradient, which otherwise split every df value in registers
+# once per tile (the fc dgrad: 49 times).  Always, since the direct fc dgrad (csrc/dconv.hip fcd_kernel,
+# which reads the planes: 195 vs 277 us at 16,384 rows); with the sg2 fc dgrad alone it measured
+# neutral-to-slower (profiles/r04_ab.txt: 1-GPU 1,152.5 vs 1,146.8 ms, per-rank 203.9 vs 201.8 ms per
+# iteration).  (Tests patch it by name.)
+PX_DF = True
 # PX g2 + the direct conv2 dgrad (round 5, PPOX_DDGRAD2=1 by default): the conv3 dgrad writes g2 as its
 # planes (bound: amax(g3) x the conv3 dgrad matrix's column norms), read as they lie by the direct
 # class-wise conv2 dgrad (csrc/dconv.hip ddgrad2_kernel: per input-pixel parity class an implicit GEMM
@@ -121,19 +116,6 @@ class PassState:
 # main stream's dgrad chain (wgrad3 || dgrad3, wgrad2 || dgrad2; the fc weight gradient ||
 # the fc dgrad), joined before the optimizer reads the gradients (PPOX_BWD_STREAMS=0: one stream)
 BWD_STREAMS = native.ab_env("PPOX_BWD_STREAMS", "1") != "0"
-BWD_SOLO_DGRAD2_BATCH = int(native.ab_env("PPOX_BWD_SOLO_DGRAD2", str(1 << 62)))
-# PPOX_FORK_LATE=1: below that batch the conv2 weight gradient's side-stream wait (on the point after the
-# conv3 dgrad) is enqueued after the conv2 dgrad's launch instead of before it — the same dependencies,
-# another capture order for a hipGraph of the pass (tools/graph_probe.py)
-FORK_LATE = native.ab_env("PPOX_FORK_LATE", "0") == "1"
-# PPOX_FORK_MERGE=1: the heads' hidden-layer weight gradient joins the fc weight gradient's fork to the side
-# stream (one main-stream event record per minibatch fewer; models.CnnActorCritic.backward_train)
-FORK_MERGE = native.ab_env("PPOX_FORK_MERGE", "0") == "1"
-# PPOX_BWD_SOLO_WGRAD2=1: from that batch conv2's weight gradient also runs alone on the main stream
-# (after the dgrad, before wgrad1) instead of beside wgrad1 — 1 % slower (same-box A/B), but its
-# event time is then its own execution time
-BWD_SOLO_WGRAD2 = native.ab_env("PPOX_BWD_SOLO_WGRAD2", "0") != "0"
-SIDE_PRIO = native.ab_env("PPOX_SIDE_PRIO", "0" if native.ab_env("PPOX_TRAIN_PRIO", "0") == "1" else "1") == "1"
 _side = {}
 
 
@@ -145,13 +127,12 @@ def side_stream(device, k=0):
         # high priority: HIP multiplexes the streams of one priority class over GPU_MAX_HW_QUEUES hardware
         # queues, and two streams on one queue run in order — in the main stream's class (the default
         # stream) a pooled stream may land on the main stream's queue, as it did once RCCL had created
-        # its streams (per-rank 196 -> 242 ms); PPOX_SIDE_PRIO=0: default priority
-        s = torch.cuda.Stream(device=device, priority=-1 if SIDE_PRIO else 0)
+        # its streams (per-rank 196 -> 242 ms)
+        s = torch.cuda.Stream(device=device, priority=-1)
         _side[(device, k)] = s
     return s
 
 
-_events = {}
 _cur_streams = {}
 
 
@@ -169,51 +150,31 @@ def current_stream(device):
     return s
 
 
-def _event(side, which):
-    # one reusable event per (side stream, direction): a wait takes the event's most recent
-    # record at the time it is enqueued, so re-recording it for the next fork / join is safe
-    ev = _events.get((side, which))
-    if ev is None:
-        ev = _events[(side, which)] = torch.cuda.Event()
-    return ev
-
-
-# PPOX_EVENT_FENCE: the fork / join events' fence — "system" (default: native events with HIP's default, a
-# system-scope release on every record), "device" (hipEventReleaseToDevice), "none" (hipEventDisableSystemFence),
-# "torch" (torch's events).  "none" ran the per-rank shape ~1 % faster (profiles/r05g: 190.9 -> 188.8 ms) and
-# was the default in round 5, but a kernel on one stream then reads another stream's fresh output stale now and
-# then: the 8-rank C4 run (tests/test_c4_gpu.py, every update teacher-forced) found non-finite df planes and
-# conv gradients in about one rank pass in 200 under it, none under "system" or one stream (round 6)
-EVENT_FENCE = native.ab_env("PPOX_EVENT_FENCE", "system")
+# The fork / join events are native events with HIP's default flags: a system-scope release on every record.
+# hipEventDisableSystemFence ran the per-rank shape ~1 % faster (profiles/r05g: 190.9 -> 188.8 ms) and was the
+# default in round 5, but a kernel on one stream then reads another stream's fresh output stale now and then:
+# the 8-rank C4 run (tests/test_c4_gpu.py, every update teacher-forced) found non-finite df planes and conv
+# gradients in about one rank pass in 200 under it, none under the system fence or one stream (round 6)
 _nevents = {}
 
 
 def _order(side, which, rec, wait):
+    # one reusable event per (side stream, direction): a wait takes the event's most recent
+    # record at the time it is enqueued, so re-recording it for the next fork / join is safe
     ev = _nevents.get((side, which))
     if ev is None:
-        flags = {"device": native.EVENT_RELEASE_TO_DEVICE, "none": native.EVENT_DISABLE_SYSTEM_FENCE}.get(EVENT_FENCE, 0)
-        ev = _nevents[(side, which)] = native.event_create(flags)
+        ev = _nevents[(side, which)] = native.event_create(0)
     native.stream_order(ev, rec, wait)
 
 
 def fork(side, cur=None):
     """side waits for everything enqueued so far on `cur` (default: the current stream)."""
-    if EVENT_FENCE != "torch":
-        _order(side, 0, cur if cur is not None else torch.cuda.current_stream(), side)
-        return
-    ev = _event(side, 0)
-    ev.record(cur)
-    side.wait_event(ev)
+    _order(side, 0, cur if cur is not None else torch.cuda.current_stream(), side)
 
 
 def join(side, cur=None):
     """`cur` (default: the current stream) waits for everything enqueued so far on side."""
-    if EVENT_FENCE != "torch":
-        _order(side, 1, side, cur if cur is not None else torch.cuda.current_stream())
-        return
-    ev = _event(side, 1)
-    ev.record(side)
-    (cur if cur is not None else torch.cuda.current_stream()).wait_event(ev)
+    _order(side, 1, side, cur if cur is not None else torch.cuda.current_stream())
 
 
 def default_math():
@@ -358,8 +319,8 @@ class NatureConvs:
             if self.math != "f32" else None
         # split math keeps conv3's output NHWC (B, 7, 7, 64): fc feature f = p * 64 + c is the
         # reference's Flatten feature c * 49 + p.  The split fc kernels are packed through that
-        # permutation; the library GEMMs (fc forward below FC_SPLIT_MIN_BATCH, fc weight grad)
-        # use this permuted f32 copy of the weight / permute their result back.
+        # permutation; the library GEMM of the fc forward below FC_SPLIT_MIN_BATCH uses this
+        # permuted f32 copy of the weight.
         self.nhwc3 = self.math != "f32"
         if self.nhwc3:
             f = torch.arange(3136, device=dev)
@@ -370,7 +331,7 @@ class NatureConvs:
         # weights, read as it lies by the conv2 forward and the direct conv2 weight gradient
         self.h1p = self.math != "f32"
         # PX planes for h2 / h3 / g3 (see PX above) where the pass's ops all run split
-        self.px = self.h1p and PX and RELU_BITS
+        self.px = self.h1p and PX
         self._ws = {}
         self._diag = None  # a dict: the backward keeps its intermediates there (tests)
         # every parameter a packed form is derived from (the conv biases: the PX bias bounds in the forms' tails)
@@ -429,22 +390,21 @@ class NatureConvs:
             return torch.empty((B, 20, 20, 64), dtype=torch.int16, device=device)
         return torch.empty((B, 20, 20, 32), device=device)
 
-    def px_h3(self, B, train):
-        """h3 as PX planes in a B-row pass: its consumers (the fc forward, and in training the fc weight
-        gradient and the fused fc dgrad reading h3's bitmask) all run the split kernels"""
-        return self.px and B >= FC_SPLIT_MIN_BATCH and (
-            not train or (B >= FC_WGRAD_SPLIT_MIN_BATCH and B < FC_DGRAD_FUSED_MAX_BATCH))
+    def px_h3(self, B):
+        """h3 as PX planes in a B-row pass: its consumers all run the split kernels (the fc forward from
+        FC_SPLIT_MIN_BATCH; in training the fc weight gradient and the fused fc dgrad, which reads h3's
+        bitmask, at every batch)"""
+        return self.px and B >= FC_SPLIT_MIN_BATCH
 
     def px_df(self, B):
         """df as PX planes (ppox_px_split) for the split fc dgrad and weight gradient"""
-        return (PX_DF and self.px and self.nhwc3 and B >= FC_WGRAD_SPLIT_MIN_BATCH
-                and B < FC_DGRAD_FUSED_MAX_BATCH)
+        return PX_DF and self.px and self.nhwc3
 
     def px_g3(self, B, am):
         """g3 as PX planes: the fc dgrad is the fused split kernel with h3's bitmask, the conv3 dgrad runs
         split with conv2's bitmask"""
         return (self.px and B >= PX_MIN_BATCH and isinstance(am, PassState) and am.bits[2] is not None and am.bits[1] is not None
-                and B < FC_DGRAD_FUSED_MAX_BATCH and self.uses_split("dgrad", 3, B) and self.uses_split("wgrad", 3))
+                and self.uses_split("dgrad", 3, B) and self.uses_split("wgrad", 3))
 
     def px_g2(self, B, am):
         """g2 as PX planes: the conv3 dgrad (split, g3's amax and conv2's bitmask) writes them, the direct
@@ -489,6 +449,10 @@ class NatureConvs:
         a Parameter, FlatParams.touch())."""
         return self.flat.write_key(self._sources)
 
+    def _pack_key(self, batch):
+        """what _forms(batch) depends on besides the trunk itself: the batch and the gates tests patch"""
+        return (batch, HEAD_SPLIT_MIN_BATCH, HEAD_FWD_SPLITK, HEAD_BWD_SPLIT_MIN_BATCH, FC_SPLIT_MIN_BATCH)
+
     def pack(self, batch=0, zero=None, in_pass=False):
         """Pack the weights (once per write to them: FlatParams.write_key) into the layouts the kernels of a
         `batch`-row pass use; a later pass of another size packs only the forms still missing
@@ -499,7 +463,7 @@ class NatureConvs:
         ~0.1 us each, this runs several times per minibatch), so a pass runs on the weights as its
         forward_acts found them."""
         flat = self.flat
-        key = (batch, HEAD_SPLIT_MIN_BATCH, HEAD_FWD_SPLITK, HEAD_BWD_SPLIT_MIN_BATCH, FC_SPLIT_MIN_BATCH)  # (tests patch these)
+        key = self._pack_key(batch)
         if in_pass and key == self._last_batch and self._quick == (flat.step_count, flat.gen):
             return False
         v = flat.write_key(self._sources)
@@ -649,18 +613,16 @@ class NatureConvs:
             if not self.pack(B, zero=table):
                 table.zero_()
         h1 = self.empty_h1(B, dev)
-        px2, px3 = px, px and self.px_h3(B, train)
+        px2, px3 = px, px and self.px_h3(B)
         h2 = torch.empty((B, 9, 9, 128), dtype=torch.int16, device=dev) if px2 else torch.empty((B, 9, 9, 64), device=dev)
         h3 = (torch.empty((B, 7, 7, 128), dtype=torch.int16, device=dev) if px3 else
               torch.empty((B, 7, 7, 64) if self.nhwc3 else (B, 64, 7, 7), device=dev))
         # the conv outputs' ReLU bitmasks where the forward and the consumer of the mask (the next
         # layer's dgrad; for conv3 the fc dgrad) both run split (training passes)
-        consumer = (self.uses_split("dgrad", 2, B), self.uses_split("dgrad", 3, B),
-                    self.nhwc3 and B < FC_DGRAD_FUSED_MAX_BATCH)
+        consumer = (self.uses_split("dgrad", 2, B), self.uses_split("dgrad", 3, B), self.nhwc3)
         # (conv1's is required on H1P, whose planes are no f32 mask)
         bits = tuple(torch.empty(B * P * C // 32, dtype=torch.int32, device=dev)
-                     if train and (RELU_BITS or (L == 1 and self.h1p)) and self.uses_split("fwd", L) and
-                     consumer[L - 1] else None
+                     if train and self.uses_split("fwd", L) and consumer[L - 1] else None
                      for L, P, C in ((1, 400, 32), (2, 81, 64), (3, 49, 64)))
         am = PassState(table, bits, (px2, px3, False, False, False))
         if B:
@@ -749,34 +711,19 @@ class NatureConvs:
         self.dgrad(3, g3, B, h2, g2, am)                        # dX of conv3, times ReLU'(conv2)
         if self._diag is not None:  # (tests: the pass's backward intermediates)
             self._diag.update(g3=g3, g2=g2, am=am)
-        # wgrad2 beside the conv2 dgrad below BWD_SOLO_DGRAD2_BATCH rows (PPOX_BWD_SOLO_DGRAD2; default: every
-        # batch); from it, the persistent conv2 dgrad runs alone — the side stream drained before it, wgrad2
-        # forked after it, beside wgrad1.  Round 4 measured the two the same at 16,384 rows; with the direct
-        # conv2 dgrad (round 5) the solo form idles the main stream ~150 µs while the side stream finishes the
-        # conv3 weight gradient: 556.4 / 557.8k vs 560.8 / 559.2k env-steps/s (profiles/r05i)
-        solo = side is not None and B >= BWD_SOLO_DGRAD2_BATCH
-        late = None
-        if side is not None and not solo:
-            if FORK_LATE:  # the fork point recorded now, the side stream's wait issued after the dgrad
-                late = _event(side, 2)
-                late.record(cur)
-            else:
-                fork(side, cur)
-                self.wgrad(2, h1, B, g2, dw2, db2, am, stream=side)
-        if solo:
-            join(side, cur)
+        # wgrad2 beside the conv2 dgrad at every batch.  The other form — the conv2 dgrad alone, the side stream
+        # drained before it, wgrad2 forked after it beside wgrad1 — measured the same at 16,384 rows in round 4;
+        # with the direct conv2 dgrad (round 5) it idles the main stream ~150 µs while the side stream finishes
+        # the conv3 weight gradient: 556.4 / 557.8k vs 560.8 / 559.2k env-steps/s (profiles/r05i)
+        if side is not None:
+            fork(side, cur)
+            self.wgrad(2, h1, B, g2, dw2, db2, am, stream=side)
         g1 = torch.empty((B, 20, 20, 32), device=dev)
         self.dgrad(2, g2, B, h1 if not self.h1p else None, g1, am)                        # dX of conv2, times ReLU'(conv1)
         if self._diag is not None:
             self._diag["g1"] = g1
-        if late is not None:
-            side.wait_event(late)
-            self.wgrad(2, h1, B, g2, dw2, db2, am, stream=side)
-        if side is None or (solo and BWD_SOLO_WGRAD2):
+        if side is None:
             self.wgrad(2, h1, B, g2, dw2, db2, am)
-        elif solo:
-            fork(side, cur)
-            self.wgrad(2, h1, B, g2, dw2, db2, am, stream=side)
         self.wgrad(1, x, B, g1, dw1, db1, am)
         if side is not None:
             join(side, cur)

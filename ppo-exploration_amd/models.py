@@ -202,13 +202,6 @@ class CnnActorCritic(nn.Module):
             iv = native.head_linear(ie, ci.weight, ci.bias).squeeze(-1)
         return out, v, iv, e, ie
 
-    def _fc_grad_buf(self, w):
-        buf = getattr(self, "_fcg", None)
-        if buf is None or buf.device != w.device:
-            buf = torch.empty_like(w)
-            self._fcg = buf
-        return buf
-
     def _wgrad_part(self, w):
         buf = getattr(self, "_wgp", None)
         if buf is None or buf.device != w.device:
@@ -259,11 +252,6 @@ class CnnActorCritic(nn.Module):
             cv = self.conv_impl
             split = cv.split_head_bwd(B)  # the extra layer's dgrad / weight gradient on the split-f16 kernels
             des = []
-            # FORK_MERGE: the hidden layers' weight gradients go to the side stream with the fc weight
-            # gradient's fork (one event record on the main stream fewer) instead of a fork of their own
-            merge = (side is not None and _convs.FORK_MERGE and split and cv.nhwc3
-                     and B >= _convs.FC_WGRAD_SPLIT_MIN_BATCH)
-            deferred = []
             # round 5: with the split hidden layer and no intrinsic head, the actor's input grad, the critic's
             # ReLU-layer grad and the hidden layer's dgrad (fc ReLU applied) in one launch (ppox_head_backward)
             # (the kernel reads w_actor as 16-B vectors; w_critic, whose flat-buffer offset depends on the action
@@ -286,17 +274,14 @@ class CnnActorCritic(nn.Module):
                 else:
                     de = torch.empty_like(act)
                     native.outer_relu_backward(d, crit.weight, act, de)  # dv * w, ReLU'
-                if merge and sp:
-                    deferred.append((de, hid))
-                else:
-                    if side is not None:  # the hidden layer's weight gradient beside the dgrad chain
-                        _convs.fork(side, cur)
-                    with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-                        if sp:
-                            native.head_hidden_wgrad(de, f, self._head_wgrad_ws(B), hid.weight.grad,
-                                                     amax_de=am[_convs.AM_DE], amax_f=am[_convs.AM_F])
-                        else:
-                            weight_grad(de, f, hid.weight.grad, self._wgrad_part(hid.weight))
+                if side is not None:  # the hidden layer's weight gradient beside the dgrad chain
+                    _convs.fork(side, cur)
+                with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+                    if sp:
+                        native.head_hidden_wgrad(de, f, self._head_wgrad_ws(B), hid.weight.grad,
+                                                 amax_de=am[_convs.AM_DE], amax_f=am[_convs.AM_F])
+                    else:
+                        weight_grad(de, f, hid.weight.grad, self._wgrad_part(hid.weight))
                 if not sp:
                     df.addmm_(de, hid.weight)
                 des.append((de, d))
@@ -326,7 +311,7 @@ class CnnActorCritic(nn.Module):
                 native.px_split(df, am[_convs.AM_DF], dfp, am.exp(_convs.EX_DF))
             if cv._diag is not None:  # (tests: the backward's intermediates)
                 cv._diag.update(df=df, dfp=dfp, de=de0)
-            if cv.nhwc3 and B >= _convs.FC_WGRAD_SPLIT_MIN_BATCH:  # split-f16 kernel, Flatten-order dW
+            if cv.nhwc3:  # split-f16 kernel, Flatten-order dW
                 h3_exp = am.exp(_convs.EX_H3)  # (PX h3: its planes)
                 df_exp = am.exp(_convs.EX_DF) if dfp is not None else None
                 dfw = dfp if dfp is not None else df
@@ -340,33 +325,20 @@ class CnnActorCritic(nn.Module):
                     # gradients' all-reduce is started from there (ordered after it and, through the
                     # fork, after every head gradient); backward_acts joins the side stream
                     _convs.fork(side, cur)
-                    for de_, hid_ in deferred:
-                        native.head_hidden_wgrad(de_, f, self._head_wgrad_ws(B), hid_.weight.grad,
-                                                 amax_de=am[_convs.AM_DE], amax_f=am[_convs.AM_F], stream=side)
                     native.nature_fc_wgrad(dfw, B, h3, self._fc_wgrad_ws(B), fc.weight.grad, amax_df=am[_convs.AM_DF],
                                            amax_h3=am[_convs.AM_H3], h3_exp=h3_exp, df_exp=df_exp, stream=side)
                     if dense_ready is not None:
                         with torch.cuda.stream(side):
                             dense_ready()
-            else:
-                if cv.nhwc3:  # NHWC features: library GEMM in NHWC order, permuted back to Flatten order
-                    dwp = self._fc_grad_buf(fc.weight)
-                    torch.mm(df.t(), hf, out=dwp)
-                    fc.weight.grad.view(fc.weight.shape[0], 64, 49).copy_(dwp.view(-1, 49, 64).transpose(1, 2))
-                else:
-                    torch.mm(df.t(), hf, out=fc.weight.grad)
+            else:  # f32 math
+                torch.mm(df.t(), hf, out=fc.weight.grad)
                 if side is not None:
                     _convs.join(side, cur)  # the hidden-layer weight gradients, before their all-reduce
                 if dense_ready is not None:
                     dense_ready()
             fe = self.feature_extractor
-            if cv.nhwc3 and B < _convs.FC_DGRAD_FUSED_MAX_BATCH:  # masked NHWC grad directly
+            if cv.nhwc3:  # masked NHWC grad directly
                 dh3, g3 = None, cv.fc_dgrad_g3(df, h3, am, dfp)
-            elif cv.nhwc3:  # library GEMM on the permuted weight: NHWC order, then the ReLU mask
-                torch.index_select(fc.weight, 1, cv.fc_perm, out=cv.wfc_nhwc)
-                g3 = torch.mm(df, cv.wfc_nhwc).view(B, 7, 7, 64)
-                native.relu_backward_(g3, h3, amax=am[_convs.AM_G3])
-                dh3 = None
             else:
                 dh3, g3 = torch.mm(df, fc.weight), None
             # conv grads are written by the trunk kernels; the flat buffer was zeroed per minibatch

@@ -183,10 +183,9 @@ def test_fold_bookkeeping_survives_the_new_key():
 def test_pack_hit_path_compares_the_full_key_once_per_pass(monkeypatch):
     """pack()'s early return: a pass's first call (forward_acts) compares the whole key, the calls inside the pass
     (in_pass) the step count and touch() generation alone — and fall through to the whole key when those moved"""
-    import convs
     net, flat, cv = _cpu_trunk()
     B = 37
-    key = (B, convs.HEAD_SPLIT_MIN_BATCH, convs.HEAD_FWD_SPLITK, convs.HEAD_BWD_SPLIT_MIN_BATCH, convs.FC_SPLIT_MIN_BATCH)
+    key = cv._pack_key(B)
     cv._version, cv._last_batch = cv.weights_key(), key  # as after a packing at B rows
     cv._quick = (flat.step_count, flat.gen)
     cv._packed = set(cv._forms(B))

@@ -14,8 +14,8 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(autouse=True)
 def _px_at_every_batch(monkeypatch):
-    """the PX machinery at every batch size (the product turns it on from convs.PX_MIN_BATCH rows),
-    df's planes included (convs.PX_DF, off in the product)"""
+    """the PX machinery at every batch size (the product turns it on from convs.PX_MIN_BATCH rows: 0),
+    df's planes included (convs.PX_DF, on in the product)"""
     import convs
     monkeypatch.setattr(convs, "PX_MIN_BATCH", 0)
     monkeypatch.setattr(convs, "PX_DF", True)

@@ -18,8 +18,6 @@ if os.environ.get("PPOX_LIB"):
 import convs  # noqa: E402
 import models  # noqa: E402
 
-convs.PX_MIN_BATCH = 0
-
 
 def t_ms(fn, iters=20):
     for _ in range(3):

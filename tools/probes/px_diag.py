@@ -14,8 +14,6 @@ from test_px_gpu import _fp64_masked, _pass, _setup  # noqa: E402
 
 def main():
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 2048
-    convs.PX_MIN_BATCH = 0
-    convs.PX_DF = True
     net, ref, flat, cv = _setup(B)
     x = torch.randint(0, 256, (B, 4, 84, 84), dtype=torch.uint8, device="cuda")
     g = torch.Generator(device="cuda").manual_seed(B + 1)
@@ -50,7 +48,6 @@ def main():
 def intermediates(B=2048):
     """f, e, amax_f of the PX-on and PX-off forward passes side by side"""
     import numpy as np
-    convs.PX_MIN_BATCH = 0
     net, ref, flat, cv = _setup(B)
     x = torch.randint(0, 256, (B, 4, 84, 84), dtype=torch.uint8, device="cuda")
     outs = {}
@@ -73,8 +70,6 @@ def intermediates(B=2048):
 def backward_intermediates(B=2048):
     """de, df and the hidden-layer weight gradient's inputs of the PX-on / PX-off passes side by side"""
     import native
-    convs.PX_MIN_BATCH = 0
-    convs.PX_DF = True
     net, ref, flat, cv = _setup(B)
     x = torch.randint(0, 256, (B, 4, 84, 84), dtype=torch.uint8, device="cuda")
     g = torch.Generator(device="cuda").manual_seed(B + 1)
