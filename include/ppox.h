@@ -560,8 +560,8 @@ int ppox_head_dgrad_outer(const float* dout, const float* w_actor, const float* 
                           uint32_t* amax_de, void* stream);
 
 /* ---------------------------------------------------------------------------
- * K6, split-f16 forms (csrc/conv_split.hip, csrc/conv.hip): the same ops, layouts and
- * fused epilogues as above, on the f16 matrix cores (v_mfma_f32_32x32x16_f16).  Every f32
+ * K6, split-f16 forms (csrc/conv_split.hip, csrc/conv.hip, csrc/wgrad.hip, csrc/pack.hip):
+ * the same ops, layouts and fused epilogues as above, on the f16 matrix cores (v_mfma_f32_32x32x16_f16).  Every f32
  * operand x is scaled by a power of two 2^E per tensor (max|x| 2^E in [2^14, 2^15)) and split
  * by round-to-nearest into two fp16 planes, x 2^E = h + l + r with |r| <= 2^-24 |x 2^E|; a
  * product keeps the three terms hA hB + hA lB + lA hB (the dropped lA lB <= 2^-22 |ab|), large

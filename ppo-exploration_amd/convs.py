@@ -10,13 +10,13 @@ split-K wgrad (+ bias grad, deterministic fixed-order reduction) kernels.
 Math modes (PPOX_CONV_MATH, default "split"):
   "split" — f32 operands scaled per tensor by a power of two and split into two fp16
             planes on the f16 matrix cores, three products per multiply (csrc/conv.hip,
-            csrc/conv_split.hip): fp32-class accuracy (at or below the f32-MFMA kernels'
+            csrc/conv_split.hip, csrc/dconv.hip, csrc/wgrad.hip): fp32-class accuracy (at or below the f32-MFMA kernels'
             error vs fp64, tests/test_kernels_gpu.py).  The per-tensor scales come from
             "amax slots" that each producing kernel records into (one zeroed table per
             forward pass, AM_* rows below).  Ops without a split kernel yet use "f32".
   "split_all" — every op that has a split kernel, including those measured slower
             than their f32 kernel at the training batch (SPLIT_SLOWER; tests).
-  "f32"   — v_mfma_f32_32x32x2_f32: every product an exact f32 FMA (csrc/conv.hip).
+  "f32"   — v_mfma_f32_32x32x2_f32: every product an exact f32 FMA (csrc/conv_f32.hip).
 """
 import os
 

@@ -1,6 +1,8 @@
-// Definitions shared by the NatureCNN conv translation units (conv.hip: f32 MFMA and
-// split-f16 kernels; conv_split.hip: the conv1 split forward) and the ICM kernels (the
-// split-bf16 helpers).  Not part of the ABI.
+// Definitions shared by the NatureCNN conv translation units (conv_f32.hip: the f32 MFMA math
+// mode; conv.hip: the split-f16 GEMM and its users; wgrad.hip: the weight gradients; pack.hip:
+// weight packing, amax, PX split; conv_split.hip: the conv1 split forward; dconv.hip: the direct
+// forms; gemm_layout.h: what only the GEMM units share) and the ICM kernels (the split-bf16
+// helpers).  Not part of the ABI.
 #pragma once
 #include "common.h"
 
@@ -386,12 +388,27 @@ struct WArgs {
     const int* gexp = nullptr;
 };
 
+// compute units of the current device (0: no device); the persistent kernels launch one workgroup per CU
+inline int cu_count() {
+    static int cus[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    if (cus[dev] == 0 && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+        cus[dev] = 0;
+    return cus[dev];
+}
+
 }  // namespace
 
+// host launchers and queries one conv unit offers the others (each kernel lives in one unit)
 namespace ppox_conv {
+// split-f16 weight packing (pack.hip): ppox_nature_pack_split's body, the planes of a packed form, and whether
+// a packed form's tail holds a finite PX bias bound
 int pack_split(const float* w1, const float* w2, const float* w3, uint16_t* q1, uint16_t* q2, uint16_t* q3,
                uint16_t* qd2, uint16_t* qd3, hipStream_t s);
 long long planes(int which);  // uint16 planes of a split-packed form (1, 2, 3, 12, 13; 4 = fc)
+bool px_bound_ok(const void* q);
+// the sg2 conv2 / conv3 split forwards (conv.hip), called from conv_split.hip's entry point
 int split_fwd23(int32_t layer, const void* x, int64_t batch, const uint16_t* wq, const float* bias, float* y,
                 const uint32_t* amax_x, uint32_t* amax_y, uint32_t* relu_bits, const int* x_exp, int* y_exp_out,
                 hipStream_t s);
@@ -432,4 +449,8 @@ bool dwgrad3_enabled(long long batch);
 long long dwgrad3_grid(long long batch);
 int dwgrad3(const void* h2p, const void* g3p, int64_t batch, const int* h_exp, const int* g_exp, float* slab,
             float* bslab, hipStream_t s);
+// the conv weight gradients' slab reduce (wgrad.hip wgrad_reduce): `splits` slabs [K][COUT] and bias slabs [COUT]
+// of layer 1, 2 or 3 summed in a fixed order into dw [co][ci][ky][kx] and db (conv1's slabs in (ci, ky, kx) K
+// order, conv2 / conv3's in (ky, kx, ci))
+int wgrad_reduce(int layer, const float* slab, const float* bslab, int splits, float* dw, float* db, hipStream_t s);
 }  // namespace ppox_conv

@@ -7,7 +7,7 @@
 // added once in the epilogue and unscaled by an exact power of two.  conv1's input is a uint8 frame (0..255),
 // exact in ONE f16 plane, so the conv1 forward and weight gradient need only two products (x wh + x wl).
 // Accuracy is therefore that of an f32 FMA chain up to summation order (tests: tests/test_kernels_gpu.py,
-// split vs f32 MFMA vs fp64).  Same layers, layouts and fused epilogues as conv.hip.
+// split vs f32 MFMA vs fp64).  Same layers, layouts and fused epilogues as conv_f32.hip.
 #include <algorithm>
 
 #include "conv_common.h"

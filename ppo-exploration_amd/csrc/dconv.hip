@@ -1809,15 +1809,6 @@ __global__ void __launch_bounds__(256, 1) dwgrad3_kernel(W3PArgs a) {
     }
 }
 
-int dconv_cus() {
-    static int cus[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    if (cus[dev] == 0 && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cus[dev] = 0;
-    return cus[dev];
-}
-
 bool env_on(const char* name, long long batch, bool dflt, long long dflt_min = 1) {
     const char* e = ppox::ab_env(name);
     if (!(e ? e[0] != '0' : dflt)) return false;
@@ -1829,7 +1820,7 @@ bool env_on(const char* name, long long batch, bool dflt, long long dflt_min = 1
 
 template <class F>
 int launch_dconv(const Args& a, const uint16_t* wq, hipStream_t s, const char* name) {
-    const int cus = dconv_cus();
+    const int cus = cu_count();
     PPOX_REQUIRE(cus > 0, "%s: no device", name);
     PPOX_REQUIRE(a.xexp && a.yexp_out && a.amax_x && a.ybias && a.ynorm, "%s: the direct form needs PX operands",
                  name);
@@ -1895,7 +1886,7 @@ int dconv_fwd(int layer, const void* x, int64_t batch, const uint16_t* wq, const
 // the conv2 dgrad on PX g2 (one workgroup per CU, each a contiguous range of samples)
 int ddgrad2(const void* g2p, int64_t batch, const uint16_t* wqd2, float* g1, const uint32_t* relu_bits,
             uint32_t* amax_g1, const int* g_exp, const int* wexp, hipStream_t s) {
-    const int cus = dconv_cus();
+    const int cus = cu_count();
     PPOX_REQUIRE(cus > 0, "ppox_nature_conv_dgrad_split: no device");
     PPOX_REQUIRE(ppox::aligned16(g2p) && ppox::aligned16(g1) && ppox::aligned16(relu_bits) && g_exp && wexp,
                  "ppox_nature_conv_dgrad_split: the direct conv2 dgrad needs 16B-aligned g2 planes, g1, bitmask");
@@ -1941,7 +1932,7 @@ int head_backward(const float* dout, const float* wa, const float* dv, const flo
                   const uint16_t* qhd, const int* wexp, int64_t rows, int n_out, float* df, float* de,
                   uint32_t* amax_de, uint32_t* amax_df, hipStream_t s) {
     if (rows == 0) return PPOX_OK;
-    const int cus = dconv_cus();
+    const int cus = cu_count();
     PPOX_REQUIRE(cus > 0, "ppox_head_backward: no device");
     PPOX_REQUIRE(n_out >= 1 && n_out <= 8, "ppox_head_backward: n_out must be 1..8");
     PPOX_REQUIRE(ppox::aligned16(wa) && ppox::aligned16(e) && ppox::aligned16(f) && ppox::aligned16(df) &&
@@ -1970,7 +1961,7 @@ bool ddgrad3_enabled(long long batch) { return env_on("PPOX_DDGRAD3", batch, DDG
 int ddgrad3(const void* g3p, int64_t batch, const uint16_t* wqd3, void* g2p, const uint32_t* amax_g3,
             uint32_t* amax_g2, const uint32_t* relu_bits, const int* g_exp, const int* wexp, const uint32_t* ynorm,
             const uint32_t* ybias, int* y_exp_out, hipStream_t s) {
-    const int cus = dconv_cus();
+    const int cus = cu_count();
     PPOX_REQUIRE(cus > 0, "ppox_nature_conv_dgrad_split: no device");
     PPOX_REQUIRE(ppox::aligned16(g3p) && ppox::aligned16(g2p) && relu_bits && g_exp && wexp && y_exp_out && amax_g3 &&
                      ynorm && ybias,
@@ -1991,7 +1982,7 @@ int ddgrad3(const void* g3p, int64_t batch, const uint16_t* wqd3, void* g2p, con
 
 // the conv3 weight gradient's direct form (PPOX_DWGRAD3=0: the im2col split form; _MIN: the smallest batch)
 bool dwgrad3_enabled(long long batch) { return env_on("PPOX_DWGRAD3", batch, DWGRAD3_DEFAULT); }
-long long dwgrad3_grid(long long batch) { return std::min<long long>(batch, dconv_cus()); }
+long long dwgrad3_grid(long long batch) { return std::min<long long>(batch, cu_count()); }
 int dwgrad3(const void* h2p, const void* g3p, int64_t batch, const int* h_exp, const int* g_exp, float* slab,
             float* bslab, hipStream_t s) {
     const long long grid = dwgrad3_grid(batch);
@@ -2011,7 +2002,7 @@ bool dfcd_enabled(long long batch) { return env_on("PPOX_DFCD", batch, DFCD_DEFA
 int dfcd(const void* dfp, int64_t batch, const uint16_t* wq, float* g3, const uint32_t* amax_df, uint32_t* amax_g3,
          const uint32_t* relu_bits, int* g3_exp_out, const int* df_exp, const int* wexp, const uint32_t* ynorm,
          const uint32_t* ybias, hipStream_t s) {
-    const int cus = dconv_cus();
+    const int cus = cu_count();
     PPOX_REQUIRE(cus > 0, "ppox_nature_fc_dgrad: no device");
     Args a{dfp, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, g3, batch, amax_df, amax_g3, wexp};
     a.bits_mask = relu_bits;

@@ -589,7 +589,7 @@ def nature_conv_fwd(layer, x, batch, idx, T, N_env, x_sample_stride, wp, bias, y
          _p(wp), _p(bias), _p(y), stream_ptr(stream))
 
 
-# split-f16 forms (csrc/conv_split.hip, csrc/conv.hip): weights packed as two fp16 planes
+# split-f16 forms (csrc/conv_split.hip, csrc/conv.hip, csrc/wgrad.hip, csrc/pack.hip): weights packed as two fp16 planes
 # (int16 tensors) times a power-of-two scale; f32 operands carry "amax slots" (include/ppox.h)
 AMAX_SLOTS = 256  # include/ppox.h ppox_amax_slots()
 PACK_TAIL32 = 2 * AMAX_SLOTS + 8  # uint32 tail of a split-packed buffer (amax partials, exponents, PX bounds)

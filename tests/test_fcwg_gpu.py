@@ -1,4 +1,4 @@
-"""The fc weight gradient, direct (round 6, csrc/conv.hip fcwg_kernel): dW = df^T h3 on PX df
+"""The fc weight gradient, direct (round 6, csrc/wgrad.hip fcwg_kernel): dW = df^T h3 on PX df
 and PX h3 — 256 outputs x 2 pixels per workgroup over a fifth of the rows, 5 split-K slabs — in Flatten order.
 Its k order and tiling are not the split wgrad form's (PPOX_FCWG=0: wgrad_split_kernel<GFc> on the same planes),
 so it is held to float64: no larger than twice the error of torch's f32 GEMM and of the split wgrad form on the

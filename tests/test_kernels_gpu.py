@@ -395,7 +395,7 @@ def test_adam_clip_vs_torch(max_norm):
 
 # ----------------------------------------------------------------- K6 convs
 def _h1p_exponent(w1, b1):
-    """E of H1P (csrc/conv.hip h1p_exp_kernel): the bound 255 max_c sum_k |W1[c][k]| + |b1[c]|
+    """E of H1P (csrc/pack.hip h1p_exp_block): the bound 255 max_c sum_k |W1[c][k]| + |b1[c]|
     (uint8 frames) with a 2^-10 margin, scaled into [2^14, 2^15)."""
     bound = (255.0 * w1.double().abs().reshape(32, -1).sum(1) + b1.double().abs()).max().item()
     m = np.float32(bound * (1.0 + 1.0 / 1024.0))

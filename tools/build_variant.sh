@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build a libppox variant with extra -D flags for kernel A/B timing (dev tool).
-# Usage: tools/build_variant.sh NAME "-DFC_NB=128 -DWS_KT2=64"
+# Usage: tools/build_variant.sh NAME "-DFCW_MIN=4096"   (a macro the sources still guard with #ifndef: csrc/dconv.hip)
 set -e
 name=$1; shift
 root=$(cd "$(dirname "$0")/.." && pwd)

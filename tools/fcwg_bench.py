@@ -1,4 +1,4 @@
-"""Timing of the fc weight gradient on PX df / PX h3: the direct form (csrc/conv.hip fcwg_kernel) against the
+"""Timing of the fc weight gradient on PX df / PX h3: the direct form (csrc/wgrad.hip fcwg_kernel) against the
 split wgrad form (PPOX_FCWG=0), slab reduce included; HIP events on the launch stream, one JSON line per batch.
 Usage: python tools/fcwg_bench.py [B ...]"""
 import json
