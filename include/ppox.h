@@ -300,6 +300,43 @@ int ppox_catch_env_step(const uint8_t* obs_in, uint8_t* obs_out, const int32_t* 
                         int32_t* ep_len, float* done_ret, int32_t* done_len, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * KeyDoor-v0, a sparse-reward pixel gridworld (csrc/env_grid.hip; DESIGN.md §11 is the
+ * specification).  Catch's geometry: a 12 x 12 grid of 7 x 7-pixel cells, obs (N, 4, 84, 84)
+ * u8 frame stacks (16B aligned, handled as ppox_catch_env_step's; obs_in == obs_out is
+ * allowed).  The border ring is wall, column 6 a dividing wall with one door cell; the
+ * layout is one per seed, from philox({0xFFFFFFFF, 0xFFFFFFFF, 0, 0xFFFFFFFF}, seed) = w:
+ * door row 1 + w.x % 10, key cell (1 + w.y % 10, 1 + (w.y >> 16) % 5) in the left room,
+ * goal cell (1 + w.z % 10, 7 + (w.z >> 16) % 4) in the right room.  ppox_keydoor_layout
+ * (host only, no HIP call) writes out5 = door row, key row, key column, goal row, goal
+ * column.
+ *
+ * state (N, 4) i32 = row, column, has_key, 0; episode (N,) i32.  An episode starts at
+ * (1 + x % 10, 1 + y % 5) of philox({0xFFFFFFFF, env_offset + n, episode index,
+ * 0xFFFFFFFF}, seed), has_key = (start == key cell); env_offset + N < 0xFFFFFFFF keeps
+ * every env id off the layout's counter.  actions (N,) int32 in {stay, up (row - 1), down
+ * (row + 1), left (column - 1), right (column + 1)}, any other value is stay.  A move onto
+ * a wall cell, or onto the door cell without the key, is refused; standing on the key cell
+ * sets has_key; reward 1 on the goal cell, else 0; done = goal reached || ep_len + 1 >=
+ * max_len (without ep_len the length counts as 0).  On done the episode is recorded,
+ * episode[n] incremented, the start redrawn, the stack zeroed and the new frame written
+ * last.  Frame cell values, a later one winning a shared cell: floor 0, wall 64, door 96
+ * and key 192 (both 0 once has_key), goal 160, agent 255.
+ *
+ * visits (2, 12, 12) i64 = [has_key][row][column], owned by the caller, never zeroed here:
+ * the reset counts every start state, a step the state it reaches (before any reset) and,
+ * on done, the new start state too.  Integer atomic adds: exact in any order.
+ * -------------------------------------------------------------------------*/
+int ppox_keydoor_layout(uint64_t seed, int32_t* out5);
+int ppox_keydoor_env_reset(uint8_t* obs, int32_t* state, int32_t* episode, int64_t* visits,
+                           int64_t N, int64_t env_offset, uint64_t seed, float* ep_ret,
+                           int32_t* ep_len, void* stream);
+int ppox_keydoor_env_step(const uint8_t* obs_in, uint8_t* obs_out, const int32_t* actions,
+                          int32_t* state, int32_t* episode, int64_t* visits, int64_t N,
+                          int64_t env_offset, uint64_t seed, int32_t max_len, float* rewards,
+                          uint8_t* dones, float* ep_ret, int32_t* ep_len, float* done_ret,
+                          int32_t* done_len, void* stream);
+
+/* ---------------------------------------------------------------------------
  * K6  NatureCNN convolutions (checkpoint models-checkpoint.py:52-58) and their
  * backward, as fp32 MFMA implicit GEMMs (v_mfma_f32_32x32x2_f32).
  *   layer 1: x = uint8 frames (batch, 4, 84, 84) [or rollout rows through idx:

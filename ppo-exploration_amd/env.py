@@ -10,7 +10,9 @@ global env index.  `make_env` keeps the reference's name and env_id argument.
 
 `make_env(..., dynamics="real")` is the opt-in alternative where the task itself is a
 few closed-form equations: the gym classic-control tasks (DeviceControlEnv) and Catch,
-a pixel task of the Atari shape (DeviceCatchEnv), stepped by csrc/env_real.hip.
+a pixel task of the Atari shape (DeviceCatchEnv), stepped by csrc/env_real.hip, and
+KeyDoor-v0, a sparse-reward pixel gridworld of the same shape with a visit-count table
+(DeviceKeyDoorEnv, csrc/env_grid.hip).
 """
 import math
 
@@ -277,6 +279,53 @@ class DeviceCatchEnv(DeviceAtariEnv):
                               self.seed, rewards, dones, self.ep_ret, self.ep_len, done_ret, done_len)
 
 
+GRID_ENVS = ("KeyDoor-v0",)
+
+
+class DeviceKeyDoorEnv(DeviceAtariEnv):
+    """KeyDoor-v0, a sparse-reward pixel gridworld of the Atari observation shape (csrc/env_grid.hip,
+    DESIGN.md §11): a 12 x 12 grid of 7 x 7-pixel cells in two rooms; the agent starts in the left
+    room, has to step on the key cell, pass the door in the dividing wall (shut without the key) and
+    reach the goal cell in the right room: reward 1 there, 0 everywhere else, episodes of at most
+    `max_len` steps.  Actions stay / up / down / left / right.  `layout` (door_row, key, goal) is one
+    per seed, shared by every env and episode.  `state` is (N, 4) int32 = row, column, has_key, 0;
+    `episode` the per-env episode index, the Philox counter of the start draw (no host step counter:
+    step_into_dc ignores the counter it is handed); `visits` (2, 12, 12) int64 counts every
+    (has_key, row, column) state entered, starts included, since the env was made."""
+
+    def __init__(self, env_id="KeyDoor-v0", n_envs=4, seed=0, env_offset=0, device="cuda", max_len=200):
+        super().__init__(env_id, n_envs, seed=seed, env_offset=env_offset, device=device)
+        self.action_space = Discrete(5)
+        self.max_len = int(max_len)
+        if self.max_len < 1:
+            raise ValueError("max_len must be positive")
+        self.layout = native.keydoor_layout(self.seed)
+        self.state = torch.zeros((n_envs, 4), dtype=torch.int32, device=self.device)
+        self.episode = torch.zeros(n_envs, dtype=torch.int32, device=self.device)
+        self.visits = torch.zeros((2, 12, 12), dtype=torch.int64, device=self.device)
+
+    def reset_into(self, obs):
+        native.keydoor_env_reset(obs, self.state, self.episode, self.visits, self.num_envs, self.env_offset, self.seed,
+                                 self.ep_ret, self.ep_len)
+        self.k = 0
+
+    def step_into(self, obs_in, obs_out, actions, rewards, dones, done_ret=None, done_len=None):
+        self.k += 1
+        native.keydoor_env_step(obs_in, obs_out, actions, self.state, self.episode, self.visits, self.num_envs,
+                                self.env_offset, self.seed, self.max_len, rewards, dones, self.ep_ret, self.ep_len,
+                                done_ret, done_len)
+
+    def step_into_dc(self, obs_in, obs_out, actions, rewards, dones, done_ret, done_len, step_base, step_off):
+        native.keydoor_env_step(obs_in, obs_out, actions, self.state, self.episode, self.visits, self.num_envs,
+                                self.env_offset, self.seed, self.max_len, rewards, dones, self.ep_ret, self.ep_len,
+                                done_ret, done_len)
+
+    def coverage(self):
+        """Number of distinct (has_key, row, column) states visited so far: the non-zero entries of
+        `visits`.  One host sync: call it when logging, not per step."""
+        return int(torch.count_nonzero(self.visits).item())
+
+
 class VecNormalize:
     """env.py:10-11 wraps every env in stable_baselines3's VecNormalize(env,
     norm_reward=True).  SB3 is not vendored in the reference (README.md:19, unpinned;
@@ -382,13 +431,16 @@ def make_env(env_id, n_envs=4, seed=0, env_offset=0, device="cuda", normalize=Tr
     builds in env-checkpoint.py without it, are not).
 
     dynamics="real" (opt-in) steps the task's own equations instead: DeviceControlEnv for the
-    classic-control ids, wrapped the same way, and DeviceCatchEnv for "Catch-v0"."""
+    classic-control ids, wrapped the same way, DeviceCatchEnv for "Catch-v0" and DeviceKeyDoorEnv
+    (max_len=200) for "KeyDoor-v0", the sparse-reward gridworld; the pixel envs are returned unwrapped."""
     if dynamics == "real":
         if env_id == "Catch-v0":
             return DeviceCatchEnv(env_id, n_envs, seed=seed, env_offset=env_offset, device=device, **kw)
+        if env_id in GRID_ENVS:
+            return DeviceKeyDoorEnv(env_id, n_envs, seed=seed, env_offset=env_offset, device=device, **kw)
         if env_id not in CONTROL_ENVS:
             raise ValueError(f"dynamics='real' is not available for {env_id!r}: "
-                             f"supported ids are {', '.join(REAL_ENVS)}")
+                             f"supported ids are {', '.join(REAL_ENVS + GRID_ENVS)}")
         env = DeviceControlEnv(env_id, n_envs, seed=seed, env_offset=env_offset, device=device, **kw)
         return VecNormalize(env, norm_reward=True) if normalize else env
     if dynamics != "synthetic":

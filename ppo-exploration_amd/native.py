@@ -119,6 +119,10 @@ SIGNATURES = {
     "ppox_control_env_step": [_i32, _vp, _vp, _vp, _vp, _i64, _i64, _u64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ppox_catch_env_reset": [_vp, _vp, _vp, _i64, _i64, _u64, _vp, _vp, _vp],
     "ppox_catch_env_step": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ppox_keydoor_layout": [_u64, _vp],
+    "ppox_keydoor_env_reset": [_vp, _vp, _vp, _vp, _i64, _i64, _u64, _vp, _vp, _vp],
+    "ppox_keydoor_env_step": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _u64, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                              _vp],
     "ppox_nature_fc_fwd_splitk": [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
     "ppox_icm_pack_w1": [_vp, _i64, _vp, _vp],
     "ppox_icm_encode": [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -555,6 +559,27 @@ def catch_env_step(obs_in, obs_out, actions, state, episode, N, env_offset, seed
                    ep_len=None, done_ret=None, done_len=None, stream=None):
     call("ppox_catch_env_step", _p(obs_in), _p(obs_out), _p(actions), _p(state), _p(episode), N, env_offset, seed,
          _p(rewards), _p(dones), _p(ep_ret), _p(ep_len), _p(done_ret), _p(done_len), stream_ptr(stream))
+
+
+def keydoor_layout(seed):
+    """KeyDoor-v0's layout for `seed` (host only, no GPU needed): door_row, key (row, column), goal (row, column)."""
+    out = (ctypes.c_int32 * 5)()
+    rc = load().ppox_keydoor_layout(int(seed) & 0xFFFFFFFFFFFFFFFF, ctypes.cast(out, _vp))
+    if rc != 0:
+        raise NativeError(f"ppox_keydoor_layout failed ({rc}): {load().ppox_last_error().decode()}")
+    return {"door_row": out[0], "key": (out[1], out[2]), "goal": (out[3], out[4])}
+
+
+def keydoor_env_reset(obs, state, episode, visits, N, env_offset, seed, ep_ret=None, ep_len=None, stream=None):
+    call("ppox_keydoor_env_reset", _p(obs), _p(state), _p(episode), _p(visits), N, env_offset, seed, _p(ep_ret),
+         _p(ep_len), stream_ptr(stream))
+
+
+def keydoor_env_step(obs_in, obs_out, actions, state, episode, visits, N, env_offset, seed, max_len, rewards, dones,
+                     ep_ret=None, ep_len=None, done_ret=None, done_len=None, stream=None):
+    call("ppox_keydoor_env_step", _p(obs_in), _p(obs_out), _p(actions), _p(state), _p(episode), _p(visits), N,
+         env_offset, seed, int(max_len), _p(rewards), _p(dones), _p(ep_ret), _p(ep_len), _p(done_ret), _p(done_len),
+         stream_ptr(stream))
 
 
 # ---------------------------------------------------------------------------

@@ -9,7 +9,8 @@
 Keyword arguments and defaults are the reference's; added keywords:
 n_envs (the reference hard-codes 4, ppo.py:52), seed, device, env (a device env
 object; default: the synthetic env for env_id), quiet, dynamics ("synthetic";
-"real": the task's own equations, env.make_env — classic control and Catch-v0), sil_kwargs (PPO(sil=True):
+"real": the task's own equations, env.make_env — classic control, Catch-v0 and the sparse-reward
+KeyDoor-v0, whose visit-count table learn() logs as rollout/coverage), sil_kwargs (PPO(sil=True):
 size, alpha, beta, epochs, batch of the self-imitation module, sil_module.py).
 
 Per iteration on each rank:
@@ -460,6 +461,10 @@ class BaseAlgorithm:
         if len(self.ep_info_buffer) > 0:
             logger.record("rollout/ep_rew_mean", float(np.mean([e["r"] for e in self.ep_info_buffer])))
             logger.record("rollout/num_episodes", self.num_episodes)
+        if hasattr(self.env, "visits") and not self.dist.enabled:
+            # distinct states visited (one host sync per log point); under a process group every rank
+            # keeps its own table and the key is omitted
+            logger.record("rollout/coverage", self.env.coverage())
         if extra:
             for k, v in extra.items():
                 logger.record(k, v)
