@@ -551,6 +551,35 @@ int ppox_es_env_noise(int32_t T, int32_t D, uint64_t env_seed, double* xi, void*
 int ppox_es_evaluate(const double* w, const double* eps, double sigma, int64_t P, int32_t D, int32_t H1,
                      int32_t H2, int32_t A, int32_t T, uint64_t env_seed, const double* xi,
                      double* fitness, double* bc, void* stream);
+/* ES episodes on the real-dynamics control tasks (csrc/es.hip es_eval_control_kernel,
+ * csrc/control_dyn.h; DESIGN.md §8 "ES on the real-dynamics tasks"), float64 throughout.
+ * kind = PPOX_CONTROL_*; the observation size D and the head size A come from the kind:
+ * CartPole (4, 2), MountainCar (2, 3), Acrobot (6, 3), Pendulum (3, 1).  w: W0 [D][H1],
+ * W1 [H1][H2], W2 [H2][A] row-major, concatenated; eps (nullable: evaluate w itself)
+ * likewise per member, member p running w + sigma * eps[p].  One wave per member.
+ *   Start: the reset draw of ppox_control_env_reset for env id 0 and episode index
+ *     `episode` under key env_seed - every member of a call starts from the same state.
+ *   Step t = 0 .. T-1, while not terminated: the f32 observation a policy sees, widened to
+ *     f64; h1 = atan(obs W0), h2 = atan(h1 W1), z = h2 W2.
+ *     Discrete kinds: p_j = exp(z_j - max z), S = sum_j p_j in index order, q_j = p_j / S;
+ *     u = (double)u01(first word of philox4x32_10({t, member0 + p, episode,
+ *     PPOX_ES_ACT_TAG}, env_seed)); the action is the first j < A-1 with
+ *     u < q_0 + .. + q_j (running f64 sum in order), else A-1.
+ *     Pendulum: torque = (float)(2 tanh(z_0)).
+ *     Then one physics step; fitness += (double)reward; steps += 1; stop on termination.
+ *     The time limit is T itself: there is no auto-reset inside an episode.
+ *   Outputs: fitness[p]; steps[p] (nullable); bc[2p], bc[2p+1] = final state[0], state[1]
+ *     (nullable); actions_out (nullable, P x T, 4 bytes each): the int32 action, or the f32
+ *     torque for Pendulum, at the steps taken - entries at steps not taken are left
+ *     untouched.
+ * Refused: unknown kind, null w / fitness, P <= 0, T <= 0, member0 < 0, H1 or H2 outside
+ * [1, 64].  PPOX_ES_ACT_TAG differs from the reset draws' 0xFFFFFFFF and from the tags of
+ * the synthetic ES streams (0xB0B0B0B0, 0xE0E0E0E0, 0xE5E5E5E5). */
+#define PPOX_ES_ACT_TAG 0xAC7AC7ACu
+int ppox_es_evaluate_control(int32_t kind, const double* w, const double* eps, double sigma, int64_t P,
+                             int64_t member0, int32_t H1, int32_t H2, int32_t T, uint64_t env_seed,
+                             int64_t episode, double* fitness, int32_t* steps, double* bc,
+                             void* actions_out, void* stream);
 int64_t ppox_es_update_workspace_bytes(int64_t P, int64_t n_params);
 int ppox_es_update(const double* eps, const double* coef, int64_t P, int64_t n_params,
                    double* workspace, int64_t workspace_bytes, double* out, void* stream);

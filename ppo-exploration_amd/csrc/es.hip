@@ -14,6 +14,10 @@
 //                    exchanged through the wave's LDS slot.  -> fitness (episode return),
 //                    behaviour characterisation (final state[0:2], the qpos[0:2] analogue
 //                    of get_behavior_char :248-271)
+// ppox_es_evaluate_control  the same wave-per-member arctan MLP on the real-dynamics control tasks
+//                    (control_dyn.h): the state lives in registers, every lane steps it redundantly
+//                    (wave-uniform), a softmax-sampled Discrete head or the 2 tanh torque head, early
+//                    exit on termination.  -> fitness, steps, behaviour = final state[0:2], actions
 // ppox_es_update     delta[j] = sum_p c[p] eps[p][j]  (the P^T r GEMV of :237-242 with
 //                    c folding the reward / novelty mix), fixed-order two-pass reduction
 // Everything is float64, as the reference's numpy program.
@@ -21,11 +25,15 @@
 #include <cmath>
 
 #include "common.h"
+#include "control_dyn.h"
 #include "philox.h"
 
 namespace {
 
 constexpr uint32_t ENV_B_TAG = 0xB0B0B0B0u, ENV_NOISE_TAG = 0xE0E0E0E0u, EPS_TAG = 0xE5E5E5E5u;
+// counter word 3 of the real-dynamics action draw (include/ppox.h PPOX_ES_ACT_TAG): apart from the reset
+// draw's 0xFFFFFFFF under the same key, and from the tags above
+constexpr uint32_t ACT_TAG = PPOX_ES_ACT_TAG;
 constexpr int HMAX = 64;
 
 __device__ inline double u53(uint32_t hi, uint32_t lo) {
@@ -162,6 +170,126 @@ __global__ void __launch_bounds__(256) es_eval_kernel(const double* __restrict__
     }
 }
 
+template <int KIND>
+struct Head {
+    static constexpr int A = KIND == ppox::CARTPOLE ? 2 : KIND == ppox::PENDULUM ? 1 : 3;
+};
+
+// One real-dynamics episode per wave (DESIGN.md §8 "ES on the real-dynamics tasks" is the specification,
+// tests/es_control_twin.py its numpy restatement).  The MLP is es_eval_kernel's: lane l owns weight column l of
+// each layer, layer 0 is the plain add chain in index order, layer 1 the four interleaved fma chains summed
+// (c0 + c1) + (c2 + c3), the head one wave_sum per logit.  The state, the observation and the physics are
+// computed by every lane alike; the decision and the termination flag are taken from lane 0, so the branch that
+// leaves the loop is wave-uniform by construction.
+template <int KIND>
+__global__ void __launch_bounds__(256)
+    es_eval_control_kernel(const double* __restrict__ w, const double* __restrict__ eps, double sigma, long long P,
+                           long long member0, int H1, int H2, int T, uint32_t k0, uint32_t k1, uint32_t episode,
+                           double* __restrict__ fitness, int32_t* __restrict__ steps, double* __restrict__ bc,
+                           void* __restrict__ actions_out) {
+    constexpr int D = ppox::Dims<KIND>::D, A = Head<KIND>::A;
+    __shared__ double sh[4][HMAX];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long long p = (long long)blockIdx.x * 4 + wv;
+    if (p >= P) return;  // wave-uniform; only wave-local LDS below
+    double* hs = sh[wv];  // hidden activation exchange
+    const long long n = (long long)D * H1 + (long long)H1 * H2 + (long long)H2 * A;
+    const double* ep = eps ? eps + p * n : nullptr;
+    auto theta = [&](long long j) { return ep ? w[j] + sigma * ep[j] : w[j]; };
+    // this lane's weight columns (zero beyond the layer sizes)
+    double w0[D], w1[HMAX], w2[A];
+#pragma unroll
+    for (int i = 0; i < D; ++i) w0[i] = lane < H1 ? theta((long long)i * H1 + lane) : 0.0;
+#pragma unroll
+    for (int k = 0; k < HMAX; ++k)
+        w1[k] = (k < H1 && lane < H2) ? theta((long long)D * H1 + (long long)k * H2 + lane) : 0.0;
+#pragma unroll
+    for (int j = 0; j < A; ++j)
+        w2[j] = lane < H2 ? theta((long long)D * H1 + (long long)H1 * H2 + (long long)lane * A + j) : 0.0;
+    const uint32_t member = (uint32_t)(member0 + p);
+    double s[4];
+    ppox::draw_state<KIND>(s, 0u, episode, k0, k1);
+    double fit = 0.0;
+    int nstep = 0;
+    for (int t = 0; t < T; ++t) {
+        float of[D];
+        ppox::write_obs<KIND>(s, of);
+        // layer 0: h1 = arctan(obs @ W0)
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < D; ++i) acc = acc + (double)of[i] * w0[i];
+        const double h1 = lane < H1 ? atan(acc) : 0.0;
+        wave_sync();
+        hs[lane] = h1;
+        wave_sync();
+        // layer 1: h2 = arctan(h1 @ W1), the sums of es_eval_kernel
+        double c0 = 0.0, c1 = 0.0, c2 = 0.0, c3 = 0.0;
+#pragma unroll
+        for (int k = 0; k < HMAX; k += 4) {
+            if (k < H1) c0 = fma(hs[k], w1[k], c0);
+            if (k + 1 < H1) c1 = fma(hs[k + 1], w1[k + 1], c1);
+            if (k + 2 < H1) c2 = fma(hs[k + 2], w1[k + 2], c2);
+            if (k + 3 < H1) c3 = fma(hs[k + 3], w1[k + 3], c3);
+        }
+        const double h2 = lane < H2 ? atan((c0 + c1) + (c2 + c3)) : 0.0;
+        // head: z = h2 @ W2
+        double z[A];
+#pragma unroll
+        for (int j = 0; j < A; ++j) z[j] = wave_sum(h2 * w2[j]);
+        int ai = 0;
+        float af = 0.f;
+        if (KIND == ppox::PENDULUM) {
+            af = (float)(2.0 * tanh(z[0]));
+            af = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(af)));
+        } else {
+            // sample from softmax(z): inverse CDF on the running sum of q in index order
+            double m = z[0];
+#pragma unroll
+            for (int j = 1; j < A; ++j) m = z[j] > m ? z[j] : m;
+            double pj[A], S = 0.0;
+#pragma unroll
+            for (int j = 0; j < A; ++j) {
+                pj[j] = exp(z[j] - m);
+                S = S + pj[j];
+            }
+            const ppox::u32x4 r = ppox::philox4x32_10(ppox::u32x4{(uint32_t)t, member, episode, ACT_TAG}, k0, k1);
+            const double u = (double)ppox::u01(r.x);
+            double c = 0.0;
+            ai = A - 1;
+            bool found = false;
+#pragma unroll
+            for (int j = 0; j < A - 1; ++j) {
+                c = c + pj[j] / S;
+                if (!found && u < c) {
+                    ai = j;
+                    found = true;
+                }
+            }
+            ai = __builtin_amdgcn_readfirstlane(ai);
+        }
+        if (actions_out && lane == 0) {
+            if (KIND == ppox::PENDULUM)
+                static_cast<float*>(actions_out)[p * T + t] = af;
+            else
+                static_cast<int32_t*>(actions_out)[p * T + t] = ai;
+        }
+        float rew;
+        bool term;
+        ppox::physics<KIND>(s, ai, af, rew, term);
+        fit = fit + (double)rew;
+        nstep += 1;
+        if (__builtin_amdgcn_readfirstlane((int)term)) break;
+    }
+    if (lane == 0) {
+        fitness[p] = fit;
+        if (steps) steps[p] = nstep;
+        if (bc) {
+            bc[2 * p] = s[0];
+            bc[2 * p + 1] = s[1];
+        }
+    }
+}
+
 // pass 1: partial[c][j] = sum over members of chunk c (in order) of coef[p] * eps[p][j]
 __global__ void __launch_bounds__(256) es_update_partial(const double* __restrict__ eps, const double* __restrict__ coef,
                                                          long long P, long long n, int chunk,
@@ -219,6 +347,32 @@ extern "C" int ppox_es_evaluate(const double* w, const double* eps, double sigma
     else
         es_eval_kernel<32, 8><<<blocks, 256, 0, s>>>(w, eps, sigma, P, D, H1, H2, A, T, k0, k1, xi, fitness, bc);
     PPOX_LAUNCHED("ppox_es_evaluate");
+}
+
+extern "C" int ppox_es_evaluate_control(int32_t kind, const double* w, const double* eps, double sigma, int64_t P,
+                                        int64_t member0, int32_t H1, int32_t H2, int32_t T, uint64_t env_seed,
+                                        int64_t episode, double* fitness, int32_t* steps, double* bc,
+                                        void* actions_out, void* stream) {
+    PPOX_REQUIRE(ppox::known_control_kind(kind), "ppox_es_evaluate_control: unknown kind %d", (int)kind);
+    PPOX_REQUIRE(w && fitness, "ppox_es_evaluate_control: null pointer");
+    PPOX_REQUIRE(P > 0 && T > 0 && member0 >= 0,
+                 "ppox_es_evaluate_control: P and T must be positive, member0 non-negative");
+    PPOX_REQUIRE(H1 >= 1 && H1 <= HMAX && H2 >= 1 && H2 <= HMAX,
+                 "ppox_es_evaluate_control: hidden sizes must lie in [1, 64] (two hidden layers)");
+    const unsigned blocks = ppox::ceil_div(P, 4);
+    hipStream_t s = ppox::as_stream(stream);
+    const uint32_t k0 = (uint32_t)env_seed, k1 = (uint32_t)(env_seed >> 32);
+#define PPOX_EVAL(K)                                                                                              \
+    es_eval_control_kernel<K><<<blocks, 256, 0, s>>>(w, eps, sigma, P, member0, H1, H2, T, k0, k1, (uint32_t)episode, \
+                                                     fitness, steps, bc, actions_out)
+    switch (kind) {
+        case ppox::CARTPOLE: PPOX_EVAL(ppox::CARTPOLE); break;
+        case ppox::MOUNTAINCAR: PPOX_EVAL(ppox::MOUNTAINCAR); break;
+        case ppox::ACROBOT: PPOX_EVAL(ppox::ACROBOT); break;
+        default: PPOX_EVAL(ppox::PENDULUM); break;
+    }
+#undef PPOX_EVAL
+    PPOX_LAUNCHED("ppox_es_evaluate_control");
 }
 
 extern "C" int64_t ppox_es_update_workspace_bytes(int64_t P, int64_t n_params) {

@@ -17,6 +17,10 @@ Reference: evolution_strategies.py:22-101 (FeedForwardNetwork), :103-384
 The reference evaluates MuJoCo envs through gym (unavailable offline); the episodes
 here run the synthetic 'SwimmerLike' dynamics of oracle/es.py (state dim and action
 dim of the env_id, Box actions; behaviour = final state[0:2], standing in for qpos[0:2]).
+dynamics="real" (opt-in) runs the classic-control tasks of env.CONTROL_ENVS instead
+(ppox_es_evaluate_control: the task's own equations, a softmax-sampled Discrete head or the
+2 tanh torque of Pendulum, early exit on termination; every member of a generation starts
+from the same state, drawn per generation; behaviour = the real final state[0:2]).
 Multi-GPU: members sharded by index across ranks; fitness all-gathered, the partial
 update all-reduced (one n_params float64 message per generation).
 """
@@ -29,7 +33,7 @@ import torch
 import logger
 import native
 from dist import DistContext
-from env import VECTOR_ENVS, Box
+from env import CONTROL_ENVS, VECTOR_ENVS, Box
 
 
 class FeedForwardNetwork:
@@ -49,11 +53,16 @@ class FeedForwardNetwork:
         return self.env.action_space.shape[0]
 
     def predict(self, inp):
-        """:50-63 (Box): tanh(arctan-MLP(obs)); host numpy, for inspection / tests."""
+        """:50-63, :83-97: tanh(arctan-MLP(obs)) on a Box space; on a Discrete one an action drawn with
+        np.random.choice from the softmax of the logits.  Host numpy, for inspection / tests."""
         out = np.expand_dims(np.asarray(inp, np.float64).flatten(), 0)
         for w in self.weights[:-1]:
             out = np.arctan(np.dot(out, w))
-        return np.tanh(np.dot(out, self.weights[-1]).astype(float)).astype(np.double)
+        logits = np.dot(out, self.weights[-1]).astype(float)
+        if self.action_space == "Discrete":
+            e = np.exp(logits - logits.max())
+            return np.random.choice(np.arange(self.num_actions), p=(e / e.sum()).squeeze(0)).astype(int)
+        return np.tanh(logits).astype(np.double)
 
     def get_weights(self):
         return self.weights
@@ -63,7 +72,17 @@ class FeedForwardNetwork:
 
 
 class _EnvSpec:
-    def __init__(self, env_id):
+    def __init__(self, env_id, dynamics="synthetic"):
+        self.kind = None
+        if dynamics == "real":
+            if env_id not in CONTROL_ENVS:
+                raise ValueError(f"dynamics='real' is not available for {env_id!r}: "
+                                 f"supported ids are {', '.join(CONTROL_ENVS)}")
+            self.kind, _, d, self.action_space, self.max_len = CONTROL_ENVS[env_id]
+            self.observation_space = Box((d,))
+            return
+        if dynamics != "synthetic":
+            raise ValueError(f"dynamics must be 'synthetic' or 'real', not {dynamics!r}")
         d, space, max_len = VECTOR_ENVS.get(env_id, (8, Box((2,)), 1000))
         if space.__class__.__name__ != "Box":
             raise NotImplementedError("ES-NSRA runs Box action spaces (the reference's MuJoCo tasks)")
@@ -78,15 +97,16 @@ def _flat(weights):
 
 class EvolutionStrategy:
     """evolution_strategies.py:103-384 with the reference's constructor signature
-    (+ seed / episode_len / device keywords of this build)."""
+    (+ seed / episode_len / device / dynamics keywords of this build)."""
 
     def __init__(self, env_id, hidden_sizes, nsr_plateu=1.5, nsr_range=[0, 1], nsr_update=0.05, population_size=50,
                  sigma=0.1, learning_rate=0.01, decay=0.9995, novelty_param=0.5, num_threads=1, seed=0,
-                 episode_len=None, device=None):
+                 episode_len=None, device=None, dynamics="synthetic"):
         if len(hidden_sizes) != 2 or max(hidden_sizes) > 64:
             raise ValueError("device ES policy: two hidden layers of at most 64 units")
         self.env_id = env_id
-        self.env = _EnvSpec(env_id)
+        self.dynamics = dynamics
+        self.env = _EnvSpec(env_id, dynamics)
         self.hidden_sizes = list(hidden_sizes)
         self.model = FeedForwardNetwork(self.env, hidden_sizes=hidden_sizes)
         self.weights = self.model.get_weights()
@@ -110,8 +130,10 @@ class EvolutionStrategy:
         P, g, G = population_size, self.dist.rank, self.dist.world
         self.m0, self.m1 = P * g // G, P * (g + 1) // G  # this rank's members
         self.generation = 0
-        self.xi = torch.empty(self.T * self.sizes[0], dtype=torch.float64, device=self.device)
-        native.es_env_noise(self.T, self.sizes[0], self.env_seed, self.xi)
+        self.ep_len = None  # real dynamics: (P,) episode lengths of the last population evaluated
+        if self.env.kind is None:
+            self.xi = torch.empty(self.T * self.sizes[0], dtype=torch.float64, device=self.device)
+            native.es_env_noise(self.T, self.sizes[0], self.env_seed, self.xi)
 
     # ---------------------------------------------------------------- pieces
     def _get_weights_try(self, w, p):
@@ -124,11 +146,15 @@ class EvolutionStrategy:
     def _dev_weights(self, weights):
         return torch.from_numpy(_flat(weights)).to(self.device)
 
-    def _evaluate_dev(self, weights, eps=None, P=1, bc=False):
+    def _evaluate_dev(self, weights, eps=None, P=1, bc=False, member0=0, steps=None):
         D, H1, H2, A = self.sizes
         fit = torch.empty(P, dtype=torch.float64, device=self.device)
         b = torch.empty(P, 2, dtype=torch.float64, device=self.device) if bc else None
         w = weights if torch.is_tensor(weights) else self._dev_weights(weights)
+        if self.env.kind is not None:
+            native.es_evaluate_control(self.env.kind, w, eps, self.SIGMA, P, member0, H1, H2, self.T, self.env_seed,
+                                       self.generation, fit, steps, b)
+            return fit, b
         native.es_evaluate(w, eps, self.SIGMA, P, D, H1, H2, A, self.T, self.env_seed, self.xi, fit, b)
         return fit, b
 
@@ -145,10 +171,18 @@ class EvolutionStrategy:
 
     def _get_rewards(self, pool, population):
         """:179-195: fitness of every perturbation -> (P,) numpy (all ranks' members)."""
-        fit, _ = self._evaluate_dev(self._dev_weights(self.weights), population, population.shape[0])
+        real = self.env.kind is not None
+        steps = torch.empty(population.shape[0], dtype=torch.int32, device=self.device) if real else None
+        fit, _ = self._evaluate_dev(self._dev_weights(self.weights), population, population.shape[0],
+                                    member0=self.m0, steps=steps)
         if self.dist.enabled:  # members in rank order (shards may differ by one when P % world != 0)
             P, G = self.POPULATION_SIZE, self.dist.world
-            fit = self.dist.all_gather_rows(fit, [P * (g + 1) // G - P * g // G for g in range(G)])
+            rows = [P * (g + 1) // G - P * g // G for g in range(G)]
+            fit = self.dist.all_gather_rows(fit, rows)
+            if real:
+                steps = self.dist.all_gather_rows(steps, rows)
+        if real:
+            self.ep_len = steps.cpu().numpy()
         return fit.cpu().numpy()
 
     def get_behavior_char(self, weights, env=None):
@@ -219,7 +253,7 @@ class EvolutionStrategy:
         MPS = 2
         meta_population = [FeedForwardNetwork(self.env, hidden_sizes=self.hidden_sizes) for _ in range(MPS)]
         start_time = time.time()
-        archive = []
+        archive = self.archive = []  # kept on the instance for inspection
         delta_reward_buffer = deque(maxlen=10)
         novelties = []
         for iteration in range(int(total_timesteps)):
@@ -264,6 +298,8 @@ class EvolutionStrategy:
                 logger.record("reward", np.mean(self.rewards))
                 logger.record("novelty", np.mean(novelties) if len(novelties) else np.nan)
                 logger.record("n_koeff", self.novelty_param)
+                if self.ep_len is not None:
+                    logger.record("ep_len", float(np.mean(self.ep_len)))
                 logger.record("total_time", time.time() - start_time)
                 logger.dump(step=iteration + 1)
             if reward_target is not None and np.mean(self.rewards) > reward_target:

@@ -106,6 +106,8 @@ SIGNATURES = {
     "ppox_es_noise": [_i64, _i64, _i64, _i64, _u64, _vp, _vp],
     "ppox_es_env_noise": [_i32, _i32, _u64, _vp, _vp],
     "ppox_es_evaluate": [_vp, _vp, _f64, _i64, _i32, _i32, _i32, _i32, _i32, _u64, _vp, _vp, _vp, _vp],
+    "ppox_es_evaluate_control": [_i32, _vp, _vp, _f64, _i64, _i64, _i32, _i32, _i32, _u64, _i64, _vp, _vp, _vp, _vp,
+                                 _vp],
     "ppox_es_update": [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp],
     "ppox_normalize_obs_f32_ex": [_vp, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _vp, _vp],
     "ppox_vecnorm_reward": [_vp, _vp, _vp, _i64, _f64, _vp, _vp, _f64, _f64, _f64, _i32, _vp],
@@ -878,6 +880,15 @@ def es_env_noise(T, D, env_seed, xi, stream=None):
 def es_evaluate(w, eps, sigma, P, D, H1, H2, A, T, env_seed, xi, fitness, bc=None, stream=None):
     call("ppox_es_evaluate", _p(w), _p(eps), float(sigma), int(P), int(D), int(H1), int(H2), int(A), int(T),
          int(env_seed) & 0xFFFFFFFFFFFFFFFF, _p(xi), _p(fitness), _p(bc), stream_ptr(stream))
+
+
+def es_evaluate_control(kind, w, eps, sigma, P, member0, H1, H2, T, env_seed, episode, fitness, steps=None, bc=None,
+                        actions_out=None, stream=None):
+    """One real-dynamics episode per member (kind = CONTROL_*): fitness (P,) f64, steps (P,) i32, bc (P, 2) f64,
+    actions_out (P, T) int32 (f32 torques for Pendulum)."""
+    call("ppox_es_evaluate_control", int(kind), _p(w), _p(eps), float(sigma), int(P), int(member0), int(H1), int(H2),
+         int(T), int(env_seed) & 0xFFFFFFFFFFFFFFFF, int(episode), _p(fitness), _p(steps), _p(bc), _p(actions_out),
+         stream_ptr(stream))
 
 
 def es_update_workspace_bytes(P, n_params):
