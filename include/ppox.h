@@ -583,6 +583,19 @@ int ppox_es_evaluate_control(int32_t kind, const double* w, const double* eps, d
 int64_t ppox_es_update_workspace_bytes(int64_t P, int64_t n_params);
 int ppox_es_update(const double* eps, const double* coef, int64_t P, int64_t n_params,
                    double* workspace, int64_t workspace_bytes, double* out, void* stream);
+/* Per-member novelty for EvolutionStrategy(..., novelty="member") (csrc/es_novelty.hip; DESIGN.md §8
+ * "Novelty per member"): the reference's get_kNN / get_novelty (:201-222, :273-289) for P
+ * behaviours at once.  Everything is float64.  bc is P x D row-major, archive M x D row-major,
+ * S = min(K, M).  For member p and archive row m the distance is
+ *   d(p, m) = sqrt(sum over j = 0 .. D-1, in index order, of (archive[m][j] - bc[p][j])^2)
+ * with no fused multiply-add: every difference, square and partial sum is rounded on its own.
+ *   novelty[p] = (the S smallest d(p, .), added in ascending order starting from the
+ *   smallest) / S; a result <= 1e-3 is replaced by 5e-3 (get_novelty's floor).
+ * Equal distances are distinct entries: duplicated archive rows each count.
+ * Refused with PPOX_EINVAL before any HIP call: P < 1, M < 1, D outside [1, 8], K outside
+ * [1, 16], a null bc / archive / novelty. */
+int ppox_es_knn_novelty(const double* bc, int64_t P, const double* archive, int64_t M, int32_t D,
+                        int32_t K, double* novelty, void* stream);
 
 /* NatureCNN head backward (explicit training backward of CnnActorCritic, replacing the
  * autograd of nn.ReLU / Linear(H, 1) at .ipynb_checkpoints/models-checkpoint.py:60-87):

@@ -21,8 +21,13 @@ dynamics="real" (opt-in) runs the classic-control tasks of env.CONTROL_ENVS inst
 (ppox_es_evaluate_control: the task's own equations, a softmax-sampled Discrete head or the
 2 tanh torque of Pendulum, early exit on termination; every member of a generation starts
 from the same state, drawn per generation; behaviour = the real final state[0:2]).
-Multi-GPU: members sharded by index across ranks; fitness all-gathered, the partial
-update all-reduced (one n_params float64 message per generation).
+novelty="member" (opt-in, both dynamics; "scalar" is the reference's rule and the default): the population's
+launch also writes every member's behaviour, ppox_es_knn_novelty (csrc/es_novelty.hip) takes each member's mean
+distance to its K nearest rows of the archive, mirrored on the device, and the update weighs the z-scored
+novelty of the members against their z-scored fitness, c = ((1 - nu) z(r) + nu z(n)) / 2 — flat rewards
+(MountainCar short of the flag) then still move the weights, which the scalar rule cannot.
+Multi-GPU: members sharded by index across ranks; fitness (and the members' novelty) all-gathered,
+the partial update all-reduced (one n_params float64 message per generation).
 """
 import time
 from collections import deque
@@ -97,15 +102,18 @@ def _flat(weights):
 
 class EvolutionStrategy:
     """evolution_strategies.py:103-384 with the reference's constructor signature
-    (+ seed / episode_len / device / dynamics keywords of this build)."""
+    (+ seed / episode_len / device / dynamics / novelty keywords of this build)."""
 
     def __init__(self, env_id, hidden_sizes, nsr_plateu=1.5, nsr_range=[0, 1], nsr_update=0.05, population_size=50,
                  sigma=0.1, learning_rate=0.01, decay=0.9995, novelty_param=0.5, num_threads=1, seed=0,
-                 episode_len=None, device=None, dynamics="synthetic"):
+                 episode_len=None, device=None, dynamics="synthetic", novelty="scalar"):
+        if novelty not in ("scalar", "member"):
+            raise ValueError(f"novelty must be 'scalar' or 'member', not {novelty!r}")
         if len(hidden_sizes) != 2 or max(hidden_sizes) > 64:
             raise ValueError("device ES policy: two hidden layers of at most 64 units")
         self.env_id = env_id
         self.dynamics = dynamics
+        self.novelty_mode = novelty
         self.env = _EnvSpec(env_id, dynamics)
         self.hidden_sizes = list(hidden_sizes)
         self.model = FeedForwardNetwork(self.env, hidden_sizes=hidden_sizes)
@@ -131,6 +139,8 @@ class EvolutionStrategy:
         self.m0, self.m1 = P * g // G, P * (g + 1) // G  # this rank's members
         self.generation = 0
         self.ep_len = None  # real dynamics: (P,) episode lengths of the last population evaluated
+        self.member_novelty = None  # novelty="member": (P,) novelty of the last population (None: empty archive)
+        self._archive_dev, self._archive_n = None, 0  # novelty="member": the archive's device mirror
         if self.env.kind is None:
             self.xi = torch.empty(self.T * self.sizes[0], dtype=torch.float64, device=self.device)
             native.es_env_noise(self.T, self.sizes[0], self.env_seed, self.xi)
@@ -185,6 +195,44 @@ class EvolutionStrategy:
             self.ep_len = steps.cpu().numpy()
         return fit.cpu().numpy()
 
+    def _archive_push(self, b):
+        """novelty="member": append the (1, 2) device row b to the archive's device mirror, a (capacity, 2)
+        float64 buffer grown by doubling."""
+        if self._archive_dev is None or self._archive_n == self._archive_dev.shape[0]:
+            grown = torch.empty(max(16, 2 * self._archive_n), 2, dtype=torch.float64, device=self.device)
+            if self._archive_n:
+                grown[:self._archive_n] = self._archive_dev[:self._archive_n]
+            self._archive_dev = grown
+        self._archive_dev[self._archive_n] = b.reshape(2)
+        self._archive_n += 1
+
+    def _get_rewards_novelty(self, population):
+        """novelty="member": _get_rewards' launch, also asking for every member's behaviour, then the members'
+        novelty against the device archive (ppox_es_knn_novelty, K = self.K) -> (rewards (P,), novelty (P,) or
+        None while the archive is empty), all ranks' members, one copy to the host."""
+        real = self.env.kind is not None
+        n = population.shape[0]
+        steps = torch.empty(n, dtype=torch.int32, device=self.device) if real else None
+        fit, b = self._evaluate_dev(self._dev_weights(self.weights), population, n, bc=True, member0=self.m0,
+                                    steps=steps)
+        out = fit
+        if self._archive_n:
+            nov = torch.empty(n, dtype=torch.float64, device=self.device)
+            native.es_knn_novelty(b, self._archive_dev[:self._archive_n], self.K, nov)
+            out = torch.stack([fit, nov], dim=1)
+        if self.dist.enabled:
+            P, G = self.POPULATION_SIZE, self.dist.world
+            rows = [P * (g + 1) // G - P * g // G for g in range(G)]
+            out = self.dist.all_gather_rows(out, rows)
+            if real:
+                steps = self.dist.all_gather_rows(steps, rows)
+        if real:
+            self.ep_len = steps.cpu().numpy()
+        host = out.cpu().numpy()
+        if host.ndim == 1:
+            return host, None
+        return np.ascontiguousarray(host[:, 0]), np.ascontiguousarray(host[:, 1])
+
     def get_behavior_char(self, weights, env=None):
         """:248-271: final state[0:2] of an episode (the qpos[0:2] analogue) -> (1, 2)."""
         _, b = self._evaluate_dev(weights, bc=True)
@@ -229,6 +277,28 @@ class EvolutionStrategy:
             return
         # device: delta = sum_p c_p eps_p, c_p = ((1 - nu) r_p + nu * novelty) / 2
         coef = ((1 - self.novelty_param) * r + self.novelty_param * novelty) / 2 if novelty is not None else r
+        self._apply_coefficients(coef, population)
+
+    def _update_weights_member(self, rewards, population, member_novelty):
+        """novelty="member" (NSR-ES): c_p = ((1 - nu) z(r)_p + nu z(n)_p) / 2 with z(x) = (x - mean) / std (numpy's
+        population std), z = 0 where std = 0 or, for the novelty, while the archive is empty (member_novelty None).
+        Both standard deviations 0: no update and no learning-rate decay, the reference's early return."""
+        def z(x):
+            if x is None:
+                return None
+            std = x.std()
+            return None if std == 0 else (x - x.mean()) / std
+        zr, zn = z(rewards), z(member_novelty)
+        if zr is None and zn is None:
+            return
+        zero = np.zeros(self.POPULATION_SIZE)
+        nu = self.novelty_param
+        coef = ((1 - nu) * (zero if zr is None else zr) + nu * (zero if zn is None else zn)) / 2
+        self._apply_coefficients(coef, population)
+
+    def _apply_coefficients(self, coef, population):
+        """weights += learning_rate / (P sigma) * sum_p coef_p eps_p over every rank's members; decays the rate."""
+        update_factor = self.learning_rate / (self.POPULATION_SIZE * self.SIGMA)
         c = torch.from_numpy(np.ascontiguousarray(coef[self.m0:self.m1], dtype=np.float64)).to(self.device)
         P = population.shape[0]
         ws = torch.empty(native.es_update_workspace_bytes(P, self.n_params) // 8 + 1, dtype=torch.float64,
@@ -254,6 +324,8 @@ class EvolutionStrategy:
         meta_population = [FeedForwardNetwork(self.env, hidden_sizes=self.hidden_sizes) for _ in range(MPS)]
         start_time = time.time()
         archive = self.archive = []  # kept on the instance for inspection
+        member = self.novelty_mode == "member"
+        self._archive_n = 0
         delta_reward_buffer = deque(maxlen=10)
         novelties = []
         for iteration in range(int(total_timesteps)):
@@ -276,8 +348,12 @@ class EvolutionStrategy:
                 brain_idx = np.random.randint(0, MPS)
                 novelty = 1
             self.weights = [w.copy() for w in meta_population[brain_idx].get_weights()]
-            rewards = self._get_rewards(None, population)
-            self._update_weights(rewards, population, novelty)
+            if member:
+                rewards, self.member_novelty = self._get_rewards_novelty(population)
+                self._update_weights_member(rewards, population, self.member_novelty)
+            else:
+                rewards = self._get_rewards(None, population)
+                self._update_weights(rewards, population, novelty)
             meta_population[brain_idx].set_weights([w.copy() for w in self.weights])
 
             mean_reward_batch = np.mean(rewards)
@@ -291,7 +367,12 @@ class EvolutionStrategy:
                 else:
                     self.novelty_param = np.maximum(self.nsr_range[0], self.novelty_param - self.nsr_update)
             delta_reward_buffer.append(mean_reward_batch)
-            archive.append(self.get_behavior_char(self.weights))
+            if member:  # the same episode; its row also goes to the device mirror
+                b = self._evaluate_dev(self.weights, bc=True)[1]
+                self._archive_push(b)
+                archive.append(b.cpu().numpy())
+            else:
+                archive.append(self.get_behavior_char(self.weights))
             self.rewards.extend([self.evaluate(self.weights)])
             if (iteration + 1) % log_interval == 0:
                 logger.record("iteration", iteration + 1)

@@ -109,6 +109,7 @@ SIGNATURES = {
     "ppox_es_evaluate_control": [_i32, _vp, _vp, _f64, _i64, _i64, _i32, _i32, _i32, _u64, _i64, _vp, _vp, _vp, _vp,
                                  _vp],
     "ppox_es_update": [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp],
+    "ppox_es_knn_novelty": [_vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp],
     "ppox_normalize_obs_f32_ex": [_vp, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _vp, _vp],
     "ppox_vecnorm_reward": [_vp, _vp, _vp, _i64, _f64, _vp, _vp, _f64, _f64, _f64, _i32, _vp],
     "ppox_outer_relu_backward": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp],
@@ -898,6 +899,17 @@ def es_update_workspace_bytes(P, n_params):
 def es_update(eps, coef, P, n_params, workspace, out, stream=None):
     call("ppox_es_update", _p(eps), _p(coef), int(P), int(n_params), _p(workspace),
          workspace.numel() * workspace.element_size(), _p(out), stream_ptr(stream))
+
+
+def es_knn_novelty(bc, archive, K, novelty, stream=None):
+    """novelty (P,) f64 = the mean distance of each row of bc (P, D) f64 to its min(K, M) nearest rows of
+    archive (M, D) f64, floored as get_novelty does (csrc/es_novelty.hip)."""
+    assert bc.dim() == 2 and archive.dim() == 2 and bc.shape[1] == archive.shape[1]
+    assert bc.is_cuda and archive.is_cuda and novelty.is_cuda
+    assert bc.is_contiguous() and archive.is_contiguous() and novelty.is_contiguous()
+    assert bc.dtype == archive.dtype == novelty.dtype == torch.float64 and novelty.numel() == bc.shape[0]
+    call("ppox_es_knn_novelty", _p(bc), bc.shape[0], _p(archive), archive.shape[0], bc.shape[1], int(K),
+         _p(novelty), stream_ptr(stream))
 
 
 def relu_backward_(grad, act, amax=None, stream=None):
