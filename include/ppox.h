@@ -195,6 +195,41 @@ int64_t ppox_simhash_keys_u8_workspace_bytes(int64_t N);
 int ppox_simhash_keys_u8(const uint8_t* obs, int64_t N, int64_t D, int64_t obs_stride,
                          const int8_t* A8, const int32_t* rowsum, int32_t* acc, int32_t* keys,
                          void* stream);
+/* The 16 projections themselves (the embedding of the episodic bonus below): the arguments,
+ * workspace, kernels' choice and checks of ppox_simhash_keys_u8, writing
+ * sums[n * 16 + b] = sum_d A8[b, d] * obs[n * obs_stride + d] (int32, exact) instead of keys. */
+int ppox_simhash_sums_u8(const uint8_t* obs, int64_t N, int64_t D, int64_t obs_stride,
+                         const int8_t* A8, const int32_t* rowsum, int32_t* acc, int32_t* sums,
+                         void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Episodic novelty bonus (PPO(episodic=True); csrc/episodic.hip): NGU's
+ * per-episode kNN bonus on the integer embeddings above (an extension: parity is to
+ * tests/episodic_twin.py).  State, all on the device: mem (N, L, 16) int32, a ring of the
+ * current episode's embeddings per env; count (N,) int32, embeddings appended in the current
+ * episode (live rows m = min(count, L), next slot count % L; starts at 0, an episode holds
+ * fewer than 2^31 steps); dm (2,) f64 = running mean of the squared kNN distance, updates.
+ * knn, per env n: d2_j = sum_i (emb[n][i] - mem[n][j][i])^2 over the m live rows, exact in
+ * int64 (|emb| < 2^27); k = min(K, m); dk[n][0..k) = the k smallest d2 ascending as f64
+ * (round to nearest), dk[n][k..K) = 0; kfound[n] = k; mk[n] = (dk[n][0] + dk[n][1] + ...,
+ * in that order) / k, 0 when k == 0.  Duplicated rows are distinct neighbours.  Then emb[n]
+ * goes to slot count % L and count += 1, or count = 0 if done[n] != 0 (the state whose
+ * transition ended the episode is that episode's last).
+ * reward, f64 without contraction: n_valid = #{kfound > 0}; S = the adjacent-pair tree sum
+ * over the env index of mk (0 where kfound == 0; padded with zeros to a power of two,
+ * s[i] = s[2i] + s[2i+1] per level); if n_valid > 0: mu = S / n_valid, dm[0] = mu if
+ * dm[1] == 0 else decay * dm[0] + (1 - decay) * mu, dm[1] += 1.  Per valid env, with the
+ * updated dm[0]: q_i = dm[0] > 0 ? dk[n][i] / dm[0] : 0; q_i = max(q_i - xi, 0);
+ * s = sqrt(sum_{i<k} eps / (q_i + eps), ascending i) + c; r = s > smax ? 0 : 1 / s; other
+ * envs r = 0.  bonus[n] = (float)r; rewards[n] = rewards[n] + (float)(beta * r), one f32 add.
+ * Refused with PPOX_EINVAL before any HIP call: a null pointer, N or L outside [1, 2^31),
+ * K outside [1, 16]. */
+int ppox_episodic_knn(const int32_t* emb, const uint8_t* done, int64_t N, int64_t L, int32_t K,
+                      int32_t* mem, int32_t* count, double* dk, int32_t* kfound, double* mk,
+                      void* stream);
+int ppox_episodic_reward(const double* dk, const int32_t* kfound, const double* mk, int64_t N,
+                         int32_t K, double* dm, double decay, double beta, double eps, double xi,
+                         double c, double smax, float* rewards, float* bonus, void* stream);
 
 /* ---------------------------------------------------------------------------
  * K5  Minibatch gather (buffer.py:41-52, 256-267): dst[r] = rollout row of the

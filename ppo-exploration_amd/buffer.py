@@ -42,6 +42,11 @@ def _to_dev(x, device, dtype=None):
     return t.to(dtype) if dtype is not None else t
 
 
+# PPO(episodic=True)'s episodic_kwargs and their defaults (NGU's constants; capacity: PPO passes the env's max_len)
+EPISODIC_DEFAULTS = {"k": 10, "capacity": 256, "beta": 0.1, "eps": 1e-3, "xi": 8e-3, "c": 1e-3, "smax": 8.0,
+                     "decay": 0.99, "frames": "last"}
+
+
 class BaseBuffer:
     """buffer.py:13-109 (size / reset / swap_and_flatten semantics)."""
 
@@ -69,7 +74,7 @@ class RolloutStorage(BaseBuffer):
     _fields = ("observations", "actions", "old_values", "old_log_probs", "advantages", "returns")
 
     def __init__(self, buffer_size, n_envs, obs_space, action_space, gae_lam=0.95, gamma=0.99, sim_hash=False,
-                 device="cuda", obs_dtype=None, draw_hash_matrix=True, hash_seed=0):
+                 device="cuda", obs_dtype=None, draw_hash_matrix=True, hash_seed=0, episodic=None):
         super().__init__(buffer_size, obs_space, action_space, n_envs=n_envs)
         self.gae_lam = gae_lam
         self.gamma = gamma
@@ -121,7 +126,54 @@ class RolloutStorage(BaseBuffer):
         self.done_len = torch.zeros((T, N), dtype=torch.int32, device=d)
         self.generator_ready = False
         self.RolloutSample = namedtuple("RolloutSample", list(self._fields))
+        self.do_episodic = episodic is not None and episodic is not False
+        if self.do_episodic:
+            self._init_episodic(dict(episodic) if isinstance(episodic, dict) else {}, hash_seed)
         self.reset()
+
+    def _init_episodic(self, kw, seed):
+        """The episodic bonus's state (`episodic`: a dict of EPISODIC_DEFAULTS' keys, or
+        True for the defaults).  It outlives reset(): episodes span rollouts."""
+        if self.obs_dtype != torch.uint8:
+            raise NotImplementedError("episodic=True embeds uint8 observations through the int8 hash matrix; got "
+                                      f"{self.obs_dtype} observations of shape {self.obs_shape}")
+        if self.do_hash:
+            raise NotImplementedError("episodic=True with sim_hash=True: two bonuses written into the same rewards "
+                                      "are not implemented")
+        unknown = sorted(set(kw) - set(EPISODIC_DEFAULTS))
+        if unknown:
+            raise TypeError(f"episodic_kwargs: unknown keys {unknown} ({', '.join(EPISODIC_DEFAULTS)})")
+        cfg = dict(EPISODIC_DEFAULTS, **kw)
+        K, L, frames = int(cfg["k"]), int(cfg["capacity"]), cfg["frames"]
+        if not 1 <= K <= 16 or L < 1:
+            raise ValueError(f"episodic_kwargs: k must lie in [1, 16] and capacity be positive (k {K}, capacity {L})")
+        if frames == "last":
+            if len(self.obs_shape) != 3:
+                raise ValueError(f"episodic_kwargs: frames='last' needs (frames, H, W) observations, not "
+                                 f"{self.obs_shape}")
+            D = int(np.prod(self.obs_shape[1:]))
+            self.epi_offset = (self.obs_shape[0] - 1) * D       # the newest frame, read in place
+        elif frames == "stack":
+            D, self.epi_offset = int(np.prod(self.obs_shape)), 0
+        else:
+            raise ValueError(f"episodic_kwargs: frames must be 'last' or 'stack', not {frames!r}")
+        T, N, d = self.buffer_size, self.n_envs, self.device
+        self.epi_k, self.epi_capacity, self.epi_frames, self.epi_D = K, L, frames, D
+        self.epi_coef = tuple(float(cfg[x]) for x in ("decay", "beta", "eps", "xi", "c", "smax"))
+        self.epi_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.epi_A8 = torch.empty((16, D), dtype=torch.int8, device=d)
+        self.epi_rowsum = torch.empty(16, dtype=torch.int32, device=d)
+        native.simhash_matrix_i8(D, self.epi_seed, self.epi_A8, self.epi_rowsum)
+        self.epi_workspace = torch.empty(native.simhash_keys_u8_workspace_bytes(N) // 4, dtype=torch.int32, device=d)
+        self.epi_emb = torch.zeros((N, 16), dtype=torch.int32, device=d)
+        self.mem = torch.zeros((N, L, 16), dtype=torch.int32, device=d)
+        self.count = torch.zeros(N, dtype=torch.int32, device=d)
+        self.dm = torch.zeros(2, dtype=torch.float64, device=d)
+        self.epi_dk = torch.zeros((N, K), dtype=torch.float64, device=d)
+        self.epi_kfound = torch.zeros(N, dtype=torch.int32, device=d)
+        self.epi_mk = torch.zeros(N, dtype=torch.float64, device=d)
+        # this rollout's bonus before beta, row t written by the step on obs_slots[t]
+        self.episodic_bonus = torch.zeros((T, N), device=d)
 
     @property
     def observations(self):
@@ -151,6 +203,8 @@ class RolloutStorage(BaseBuffer):
         if self.do_hash:
             self.sim_hash(self.obs_slots[t], self.rewards[t], t)
         self.masks[t].copy_(_to_dev(mask, self.device).reshape(self.n_envs))
+        if self.do_episodic:
+            self.episodic(self.obs_slots[t], self.rewards[t], self.masks[t], t)
         self.values[t].copy_(_to_dev(value, self.device).reshape(self.n_envs))
         self.pos += 1
         if self.pos == self.buffer_size:
@@ -181,6 +235,26 @@ class RolloutStorage(BaseBuffer):
         else:
             keys_all, offset, total = keys, 0, self.n_envs
         native.simhash_apply(keys_all, total, offset, self.n_envs, self.count_table, self.beta, rewards)
+        return rewards
+
+    def episodic(self, obs, rewards, dones, t=None):
+        """The episodic novelty bonus of one step, three launches on preallocated buffers
+        (graph-capturable): the integer embedding of `obs` (uint8 frames read in place, the newest frame or
+        the whole stack) -> the k nearest of the env's episode so far, then the embedding appended and the
+        memory emptied where `dones` (uint8) is set -> the bonus into episodic_bonus[t] (t: the step, default
+        pos) and beta times it added to `rewards` (this rank's (n_envs,) f32 row, mutated and returned)."""
+        x = obs.reshape(self.n_envs, -1)
+        if x.dtype != torch.uint8 or x.stride(-1) != 1:
+            raise TypeError("episodic: this storage embeds uint8 observations with contiguous rows")
+        if self.epi_offset:
+            x = x[:, self.epi_offset:]
+        N, K = self.n_envs, self.epi_k
+        native.simhash_sums_u8(x, N, self.epi_D, x.stride(0), self.epi_A8, self.epi_rowsum, self.epi_workspace,
+                               self.epi_emb)
+        native.episodic_knn(self.epi_emb, dones, N, self.epi_capacity, K, self.mem, self.count, self.epi_dk,
+                            self.epi_kfound, self.epi_mk)
+        native.episodic_reward(self.epi_dk, self.epi_kfound, self.epi_mk, N, K, self.dm, *self.epi_coef, rewards,
+                               self.episodic_bonus[self.pos if t is None else t])
         return rewards
 
     @traced("gae")

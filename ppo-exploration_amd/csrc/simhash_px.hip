@@ -13,6 +13,8 @@
 // sides, which is all the sum over k needs.  The 4 waves' accumulators are added in LDS and stored
 // as one partial slab per (slice, env block); a second kernel adds the slabs in slice order, adds
 // 128 * rowsum and writes the keys.  Everything else (odd D, unaligned rows) takes a plain kernel.
+// ppox_simhash_sums_u8 (the episodic bonus's embedding) runs the same partial kernel and
+// a finish that stores the 16 sums themselves; its plain kernel is the keys' with the other epilogue.
 #include "common.h"
 #include "philox.h"
 
@@ -133,7 +135,23 @@ __global__ void __launch_bounds__(PX_SLAB) simhash_px_finish_kernel(const int32_
     if (e < PX_ENVS && blk * PX_ENVS + e < N) keys[blk * PX_ENVS + e] = key[e];
 }
 
-// any D, stride, alignment: one block per env
+// as the finish above, storing the sums: sums[env * 16 + b]
+__global__ void __launch_bounds__(PX_SLAB) simhash_px_finish_sums_kernel(const int32_t* __restrict__ part, long long N,
+                                                                         long long slices,
+                                                                         const int32_t* __restrict__ rowsum,
+                                                                         int32_t* __restrict__ sums) {
+    const int e = threadIdx.x;
+    const long long blk = blockIdx.x;
+    const int lane = e & 63, r = (e >> 6) & 3, t = e >> 8;
+    const int b = (lane >> 4) * 4 + r;
+    const long long env = blk * PX_ENVS + t * 16 + (lane & 15);
+    int s = 128 * rowsum[b];
+    for (long long q = 0; q < slices; ++q) s += part[(q * gridDim.x + blk) * PX_SLAB + e];
+    if (env < N) sums[env * BITS + b] = s;
+}
+
+// any D, stride, alignment: one block per env (SUMS: out[n * 16 + b] = the sums, else out[n] = the key)
+template <bool SUMS>
 __global__ void __launch_bounds__(256) simhash_px_plain_kernel(const uint8_t* __restrict__ obs, long long D,
                                                                long long stride, const int8_t* __restrict__ A8,
                                                                int32_t* __restrict__ keys) {
@@ -153,7 +171,9 @@ __global__ void __launch_bounds__(256) simhash_px_plain_kernel(const uint8_t* __
         if (lane == 0) red[wave][b] = v;
     }
     __syncthreads();
-    if (wave == 0) {
+    if (SUMS) {
+        if (threadIdx.x < BITS) keys[n * BITS + lane] = red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane];
+    } else if (wave == 0) {
         const bool set = lane < BITS && red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane] > 0;
         const unsigned long long m = __ballot(set);
         if (lane == 0) keys[n] = (int32_t)(m & 0xFFFFu);
@@ -184,7 +204,7 @@ extern "C" int ppox_simhash_keys_u8(const uint8_t* obs, int64_t N, int64_t D, in
                  "ppox_simhash_keys_u8: bad sizes");
     hipStream_t s = ppox::as_stream(stream);
     if (D % 16 != 0 || obs_stride % 16 != 0 || !ppox::aligned16(obs) || !ppox::aligned16(A8)) {
-        simhash_px_plain_kernel<<<(unsigned)N, 256, 0, s>>>(obs, D, obs_stride, A8, keys);
+        simhash_px_plain_kernel<false><<<(unsigned)N, 256, 0, s>>>(obs, D, obs_stride, A8, keys);
         PPOX_LAUNCHED("ppox_simhash_keys_u8");
     }
     const long long nblocks = (N + PX_ENVS - 1) / PX_ENVS, units = (D + PX_UNIT - 1) / PX_UNIT;
@@ -194,4 +214,24 @@ extern "C" int ppox_simhash_keys_u8(const uint8_t* obs, int64_t N, int64_t D, in
     PPOX_LAUNCHED_NORET("ppox_simhash_keys_u8");
     simhash_px_finish_kernel<<<(unsigned)nblocks, PX_SLAB, 0, s>>>(acc, N, slices, rowsum, keys);
     PPOX_LAUNCHED("ppox_simhash_keys_u8");
+}
+
+extern "C" int ppox_simhash_sums_u8(const uint8_t* obs, int64_t N, int64_t D, int64_t obs_stride, const int8_t* A8,
+                                    const int32_t* rowsum, int32_t* acc, int32_t* sums, void* stream) {
+    if (N == 0) return PPOX_OK;  // empty shard: no pointers to check
+    PPOX_REQUIRE(obs && A8 && rowsum && acc && sums, "ppox_simhash_sums_u8: null pointer");
+    PPOX_REQUIRE(N >= 0 && N <= 0x7FFFFFFFll && D >= 1 && D <= PX_MAX_D && obs_stride >= D,
+                 "ppox_simhash_sums_u8: bad sizes");
+    hipStream_t s = ppox::as_stream(stream);
+    if (D % 16 != 0 || obs_stride % 16 != 0 || !ppox::aligned16(obs) || !ppox::aligned16(A8)) {
+        simhash_px_plain_kernel<true><<<(unsigned)N, 256, 0, s>>>(obs, D, obs_stride, A8, sums);
+        PPOX_LAUNCHED("ppox_simhash_sums_u8");
+    }
+    const long long nblocks = (N + PX_ENVS - 1) / PX_ENVS, units = (D + PX_UNIT - 1) / PX_UNIT;
+    const long long per = px_units_per_wg(nblocks, units), slices = (units + per - 1) / per;
+    simhash_px_partial_kernel<<<dim3((unsigned)nblocks, (unsigned)slices), 256, 0, s>>>(obs, N, D, obs_stride, A8,
+                                                                                        units, per, acc);
+    PPOX_LAUNCHED_NORET("ppox_simhash_sums_u8");
+    simhash_px_finish_sums_kernel<<<(unsigned)nblocks, PX_SLAB, 0, s>>>(acc, N, slices, rowsum, sums);
+    PPOX_LAUNCHED("ppox_simhash_sums_u8");
 }

@@ -61,6 +61,9 @@ SIGNATURES = {
     "ppox_simhash_apply": [_vp, _i64, _i64, _i64, _vp, _f64, _vp, _vp],
     "ppox_simhash_matrix_i8": [_i64, _u64, _vp, _vp, _vp],
     "ppox_simhash_keys_u8": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
+    "ppox_simhash_sums_u8": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
+    "ppox_episodic_knn": [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ppox_episodic_reward": [_vp, _vp, _vp, _i64, _i32, _vp, _f64, _f64, _f64, _f64, _f64, _f64, _vp, _vp, _vp],
     "ppox_gather_rows": [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp],
     "ppox_grad_sumsq": [_vp, _i64, _vp, _vp],
     "ppox_adam_step": [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _f64, _f64, _f64, _f64, _i64, _vp, _vp],
@@ -457,6 +460,28 @@ def simhash_keys_u8(obs, N, D, stride, A8, rowsum, workspace, keys, stream=None)
     simhash_keys_u8_workspace_bytes(N) bytes."""
     call("ppox_simhash_keys_u8", _p(obs), N, D, stride, _p(A8), _p(rowsum), _p(workspace), _p(keys),
          stream_ptr(stream))
+
+
+def simhash_sums_u8(obs, N, D, stride, A8, rowsum, workspace, sums, stream=None):
+    """sums (N, 16) int32, the projections of uint8 rows `obs` (read in place) that simhash_keys_u8
+    takes the signs of; the same workspace."""
+    call("ppox_simhash_sums_u8", _p(obs), N, D, stride, _p(A8), _p(rowsum), _p(workspace), _p(sums),
+         stream_ptr(stream))
+
+
+def episodic_knn(emb, done, N, L, K, mem, count, dk, kfound, mk, stream=None):
+    """Per env: the K smallest squared distances of emb (N, 16) int32 to the env's ring mem (N, L, 16)
+    -> dk (N, K) f64, kfound (N,) int32, mk (N,) f64; then emb is appended and count advanced (reset
+    where done (N,) uint8 is set).  include/ppox.h has the semantics."""
+    call("ppox_episodic_knn", _p(emb), _p(done), N, L, K, _p(mem), _p(count), _p(dk), _p(kfound), _p(mk),
+         stream_ptr(stream))
+
+
+def episodic_reward(dk, kfound, mk, N, K, dm, decay, beta, eps, xi, c, smax, rewards, bonus, stream=None):
+    """The episodic bonus of one step from episodic_knn's outputs: dm (2,) f64 advanced, bonus (N,) f32
+    written, rewards (N,) f32 += beta * bonus."""
+    call("ppox_episodic_reward", _p(dk), _p(kfound), _p(mk), N, K, _p(dm), decay, beta, eps, xi, c, smax,
+         _p(rewards), _p(bonus), stream_ptr(stream))
 
 
 def categorical_sample(logits, N, A, env_offset, seed, counter, actions, log_probs, stream=None):

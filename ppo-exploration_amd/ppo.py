@@ -11,7 +11,9 @@ n_envs (the reference hard-codes 4, ppo.py:52), seed, device, env (a device env
 object; default: the synthetic env for env_id), quiet, dynamics ("synthetic";
 "real": the task's own equations, env.make_env — classic control, Catch-v0 and the sparse-reward
 KeyDoor-v0, whose visit-count table learn() logs as rollout/coverage), sil_kwargs (PPO(sil=True):
-size, alpha, beta, epochs, batch of the self-imitation module, sil_module.py).
+size, alpha, beta, epochs, batch of the self-imitation module, sil_module.py), episodic / episodic_kwargs
+(PPO(episodic=True): a per-episode kNN novelty bonus on the uint8 frames; k, capacity, beta, eps,
+xi, c, smax, decay, frames).
 
 Per iteration on each rank:
   collect: T x [net forward (rocBLAS + MFMA convs) -> ppox_categorical_sample ->
@@ -465,6 +467,10 @@ class BaseAlgorithm:
             # distinct states visited (one host sync per log point); under a process group every rank
             # keeps its own table and the key is omitted
             logger.record("rollout/coverage", self.env.coverage())
+        if getattr(self.rollout, "do_episodic", False):
+            # the rollout's mean bonus (before beta) and the running mean squared kNN distance (two host reads)
+            logger.record("rollout/episodic_bonus", float(self.rollout.episodic_bonus.mean().item()))
+            logger.record("rollout/episodic_dm", float(self.rollout.dm[0].item()))
         if extra:
             for k, v in extra.items():
                 logger.record(k, v)
@@ -504,10 +510,19 @@ class PPO(BaseAlgorithm):
     def __init__(self, *, env_id, lr=3e-4, nstep=128, batch_size=128, n_epochs=10, gamma=0.99, gae_lam=0.95,
                  clip_range=0.2, ent_coef=.01, vf_coef=1, max_grad_norm=0.2, hidden_size=128, sim_hash=False,
                  sil=False, n_envs=4, seed=0, device=None, env=None, quiet=False, dynamics="synthetic",
-                 sil_kwargs=None):
+                 sil_kwargs=None, episodic=False, episodic_kwargs=None):
         if sil and sim_hash:
             raise NotImplementedError("sil=True with sim_hash=True: the count bonus is written into the rollout's "
                                       "rewards, which self-imitation would replay as returns")
+        if episodic and sil:
+            raise NotImplementedError("episodic=True with sil=True: the episodic bonus is written into the rollout's "
+                                      "rewards, which self-imitation would replay as returns")
+        if episodic and sim_hash:
+            raise NotImplementedError("episodic=True with sim_hash=True: two bonuses written into the same rewards "
+                                      "are not implemented")
+        if episodic and DistContext.current().enabled:
+            raise NotImplementedError("episodic=True under a process group: the running mean of the kNN distance "
+                                      "(dm) is not reduced over ranks")
         if sil and DistContext.current().enabled:
             raise NotImplementedError("sil=True under a process group: the replay ring and its priority trees are "
                                       "not sharded over ranks")
@@ -516,11 +531,11 @@ class PPO(BaseAlgorithm):
                          dynamics=dynamics)
         self.policy = Policy(self.env, hidden_size)
         self.rollout = self._new_rollout(RolloutStorage, gae_lam=gae_lam, gamma=gamma, sim_hash=sim_hash,
-                                         hash_seed=seed)
+                                         hash_seed=seed, episodic=self._episodic_config(episodic, episodic_kwargs))
         self.flat = FlatParams(self.policy.net, self.device)
         self._attach_convs()
         self.optimizer = self.flat
-        self.sim_hash, self.sil = sim_hash, sil
+        self.sim_hash, self.sil, self.episodic = sim_hash, sil, bool(episodic)
         self.sil_module = None
         if sil:
             self._init_sil(dict(sil_kwargs or {}), gamma)
@@ -544,12 +559,25 @@ class PPO(BaseAlgorithm):
         self.sil_module = SilModule(size, self.policy, self.optimizer, self.local_envs, self.env, gamma=gamma,
                                     nstep=self.nstep, alpha=alpha, beta=beta, device=self.device, algo=self)
 
+    def _episodic_config(self, episodic, kw):
+        """episodic_kwargs (k, capacity, beta, eps, xi, c, smax, decay, frames: buffer.EPISODIC_DEFAULTS) for the
+        storage, None without the bonus; capacity defaults to the env's max_len where it has one."""
+        if not episodic:
+            return None
+        cfg = dict(kw or {})
+        max_len = getattr(self.env, "max_len", None)
+        if "capacity" not in cfg and max_len is not None:
+            cfg["capacity"] = int(max_len)
+        return cfg
+
     def _collect_graph_ok(self):
         # a hashing rollout is captured only for uint8 frames without a process group: the keys' all-gather
-        # stays on the eager path
+        # stays on the eager path; the episodic bonus (uint8 frames, no process group: both checked at
+        # construction) reads nothing back and is captured as it is
         ro = self.rollout
         return (self._collect_graph_enabled and isinstance(self.env, DeviceAtariEnv) and self.discrete
                 and (not ro.do_hash or (ro.hash_px and not self.dist.enabled))
+                and (not ro.do_episodic or (ro.obs_dtype == torch.uint8 and not self.dist.enabled))
                 and getattr(self.policy.net, "conv_impl", None) is not None and self.device.type == "cuda")
 
     def _collect_steps_eager(self):
@@ -563,6 +591,8 @@ class PPO(BaseAlgorithm):
                                ro.done_ret[t], ro.done_len[t])
             if ro.do_hash:                                  # rollout.add -> sim_hash(last_obs), buffer.py:176
                 ro.sim_hash(ro.obs_slots[t], ro.rewards[t], t)
+            if ro.do_episodic:
+                ro.episodic(ro.obs_slots[t], ro.rewards[t], ro.masks[t], t)
             self.num_timesteps += self.num_envs
 
     def _collect_step_dc(self, t):
@@ -580,6 +610,8 @@ class PPO(BaseAlgorithm):
                               ro.done_ret[t], ro.done_len[t], self._ctr[1:2], t + 1)
         if ro.do_hash:  # keys -> apply on preallocated buffers, the eager loop's order
             ro.sim_hash(ro.obs_slots[t], ro.rewards[t], t)
+        if ro.do_episodic:  # sums -> knn -> reward, all state on the device
+            ro.episodic(ro.obs_slots[t], ro.rewards[t], ro.masks[t], t)
 
     def _collect_graphed(self):
         """ppo.py:174-194 as one hipGraph replay: the first collect runs eagerly (packing the
@@ -668,6 +700,8 @@ class PPO(BaseAlgorithm):
 
     def learn(self, total_timesteps, log_interval, reward_target=None, log_to_file=False):
         name = "PPO_SimHash" if self.sim_hash else ("PPO_SIL" if self.sil else "PPO")
+        if self.episodic:
+            name = "PPO_Episodic"
         return self._learn(name, total_timesteps, log_interval, reward_target, log_to_file)
 
 
@@ -678,7 +712,10 @@ class PPO_RND(BaseAlgorithm):
     def __init__(self, *, env_id, lr=3e-4, nstep=128, batch_size=128, n_epochs=10, gamma=0.99, int_gamma=0.99,
                  gae_lam=0.95, clip_range=0.2, ent_coef=.01, vf_coef=0.5, int_vf_coef=0.5, max_grad_norm=0.2,
                  hidden_size=128, int_hidden_size=128, int_lr=3e-4, rnd_start=1e+3, n_envs=4, seed=0, device=None,
-                 env=None, quiet=False, dynamics="synthetic"):
+                 env=None, quiet=False, dynamics="synthetic", episodic=False):
+        if episodic:
+            raise NotImplementedError("PPO_RND with episodic=True: the episodic bonus is wired into PPO's rollout "
+                                      "only (NGU's product of the two bonuses is not implemented)")
         super().__init__(env_id, lr, nstep, batch_size, n_epochs, gamma, gae_lam, clip_range, ent_coef, vf_coef,
                          max_grad_norm, n_envs=n_envs, seed=seed, device=device, env=env, quiet=quiet,
                          dynamics=dynamics)
@@ -836,7 +873,10 @@ class PPO_ICM(BaseAlgorithm):
     def __init__(self, *, env_id, lr=3e-4, int_lr=3e-4, nstep=128, batch_size=128, n_epochs=10, gamma=0.99,
                  gae_lam=0.95, clip_range=0.2, ent_coef=.01, vf_coef=0.5, max_grad_norm=0.2, hidden_size=128,
                  int_hidden_size=32, int_rew_integration=0.05, beta=0.2, policy_weight=1, n_envs=4, seed=0,
-                 device=None, env=None, quiet=False, dynamics="synthetic"):
+                 device=None, env=None, quiet=False, dynamics="synthetic", episodic=False):
+        if episodic:
+            raise NotImplementedError("PPO_ICM with episodic=True: the episodic bonus is wired into PPO's rollout "
+                                      "only (the curiosity reward mix reads the same rewards row)")
         super().__init__(env_id, lr, nstep, batch_size, n_epochs, gamma, gae_lam, clip_range, ent_coef, vf_coef,
                          max_grad_norm, n_envs=n_envs, seed=seed, device=device, env=env, quiet=quiet,
                          dynamics=dynamics)

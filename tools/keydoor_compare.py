@@ -1,5 +1,5 @@
-"""PPO, PPO(sim_hash=True), PPO_RND and PPO_ICM on KeyDoor-v0 for a fixed number of env steps and three seeds
-(DESIGN.md §11).  Every run is a fresh child process under its own `timeout`; its log points (env steps,
+"""PPO, PPO(sim_hash=True), PPO_RND, PPO_ICM and PPO(episodic=True) on KeyDoor-v0 for a fixed number of env steps and
+three seeds. Every run is a fresh child process under its own `timeout`; its log points (env steps,
 ep_rew_mean — the mean return of the last 50 episodes, which on this task is the goal rate —, coverage) go as one
 JSON line each into --out, after one line per seed with the numpy twin's random-policy goal rate at that seed and
 max_len (tests/keydoor_twin.py, CPU: the reference the learning gate is measured against).  The tool stops at the
@@ -20,6 +20,7 @@ CONFIGS = {
     "PPO_SimHash": ("PPO", {"sim_hash": True}),
     "PPO_RND": ("PPO_RND", {}),
     "PPO_ICM": ("PPO_ICM", {}),
+    "PPO_Episodic": ("PPO", {"episodic": True}),  # the defaults: k 10, capacity max_len, the newest frame
 }
 
 
@@ -43,9 +44,12 @@ def child(args):
 
     def dump(step=0):
         kv = logger.get_values()
-        print(json.dumps({"config": args.child, "seed": args.seed, "env_steps": int(kv["time/total timesteps"]),
-                          "ep_rew_mean": kv.get("rollout/ep_rew_mean"), "episodes": kv.get("rollout/num_episodes"),
-                          "coverage": kv["rollout/coverage"], "seconds": round(time.time() - t0, 2)}), flush=True)
+        row = {"config": args.child, "seed": args.seed, "env_steps": int(kv["time/total timesteps"]),
+               "ep_rew_mean": kv.get("rollout/ep_rew_mean"), "episodes": kv.get("rollout/num_episodes"),
+               "coverage": kv["rollout/coverage"], "seconds": round(time.time() - t0, 2)}
+        if "rollout/episodic_bonus" in kv:
+            row.update(episodic_bonus=kv["rollout/episodic_bonus"], episodic_dm=kv["rollout/episodic_dm"])
+        print(json.dumps(row), flush=True)
         real_dump(step)
 
     logger.dump = dump
