@@ -230,6 +230,26 @@ int ppox_episodic_knn(const int32_t* emb, const uint8_t* done, int64_t N, int64_
 int ppox_episodic_reward(const double* dk, const int32_t* kfound, const double* mk, int64_t N,
                          int32_t K, double* dm, double decay, double beta, double eps, double xi,
                          double c, double smax, float* rewards, float* bonus, void* stream);
+/* NGU's reward (PPO_NGU; DESIGN.md §4.6, parity to tests/ngu_twin.py): launched after
+ * ppox_episodic_knn in place of ppox_episodic_reward.  One workgroup, f64 without contraction.
+ * Episodic part: n_valid, S, the dm update and the per-env r exactly as ppox_episodic_reward
+ * states them; bonus[n] = (float)r; no rewards array is touched.
+ * Modulator, err == NULL (the lifelong error is not trained yet): mod_n = 1, em is neither read
+ * nor written.  err != NULL, e_n = (double)err[n] (finite): mb = tree(e) / (double)N,
+ * vb = tree((e_n - mb) * (e_n - mb)) / (double)N, tree the adjacent-pair tree over the env
+ * index of S (zero-padded to a power of two).  em (3,) f64 = running mean, variance, count of
+ * the error, merged as util.py:30-44, left to right: delta = mb - em[0]; tot = em[2] + N;
+ * em[0] = em[0] + delta * N / tot; M2 = em[1] * em[2] + vb * N + delta * delta * em[2] * N / tot
+ * (the old em[1], em[2]); em[1] = M2 / tot; em[2] = tot.  With the updated em:
+ * sigma = sqrt(em[1]); a_n = sigma > 0 ? 1 + (e_n - em[0]) / sigma : 1;
+ * mod_n = min(max(a_n, 1), mod_max).
+ * modulator[n] = (float)mod_n; int_rewards[n] = (float)(r * mod_n), a store.
+ * Refused with PPOX_EINVAL before any HIP call: a null pointer other than err, N outside
+ * [1, 2^31), K outside [1, 16], mod_max < 1. */
+int ppox_ngu_reward(const double* dk, const int32_t* kfound, const double* mk, const float* err,
+                    int64_t N, int32_t K, double* dm, double* em, double decay, double eps,
+                    double xi, double c, double smax, double mod_max, float* int_rewards,
+                    float* bonus, float* modulator, void* stream);
 
 /* ---------------------------------------------------------------------------
  * K5  Minibatch gather (buffer.py:41-52, 256-267): dst[r] = rollout row of the

@@ -45,6 +45,9 @@ def _to_dev(x, device, dtype=None):
 # PPO(episodic=True)'s episodic_kwargs and their defaults (NGU's constants; capacity: PPO passes the env's max_len)
 EPISODIC_DEFAULTS = {"k": 10, "capacity": 256, "beta": 0.1, "eps": 1e-3, "xi": 8e-3, "c": 1e-3, "smax": 8.0,
                      "decay": 0.99, "frames": "last"}
+# PPO_NGU's episodic_kwargs: the bonus is not added to the rewards (no beta) and is multiplied by a modulator in
+# [1, mod_max] (NGU's L)
+NGU_DEFAULTS = dict({k: v for k, v in EPISODIC_DEFAULTS.items() if k != "beta"}, mod_max=5.0)
 
 
 class BaseBuffer:
@@ -204,11 +207,15 @@ class RolloutStorage(BaseBuffer):
             self.sim_hash(self.obs_slots[t], self.rewards[t], t)
         self.masks[t].copy_(_to_dev(mask, self.device).reshape(self.n_envs))
         if self.do_episodic:
-            self.episodic(self.obs_slots[t], self.rewards[t], self.masks[t], t)
+            self._episodic_step(t)
         self.values[t].copy_(_to_dev(value, self.device).reshape(self.n_envs))
         self.pos += 1
         if self.pos == self.buffer_size:
             self.full = True
+
+    def _episodic_step(self, t):
+        """add()'s episodic step on row t (IntrinsicStorage pays the bonus on its intrinsic stream instead)."""
+        self.episodic(self.obs_slots[t], self.rewards[t], self.masks[t], t)
 
     def sim_hash(self, obs, rewards, t=None):
         """buffer.py:188-200 on the device: count bonus added to `rewards` (this rank's
@@ -305,15 +312,32 @@ class IntrinsicStorage(RolloutStorage):
                "int_advantages", "returns", "int_returns")
 
     def __init__(self, buffer_size, n_envs, obs_space, action_space, gae_lam=0.95, gamma=0.99, int_gamma=0.99,
-                 device="cuda", obs_dtype=None, draw_hash_matrix=True):
+                 device="cuda", obs_dtype=None, draw_hash_matrix=True, episodic=None, hash_seed=0):
+        do_ngu = episodic is not None and episodic is not False
+        if do_ngu:
+            # PPO_NGU: the episodic state of RolloutStorage, its bonus multiplied by a modulator
+            # and written to the intrinsic stream instead of being added to the rewards
+            episodic = dict(episodic) if isinstance(episodic, dict) else {}
+            unknown = sorted(set(episodic) - set(NGU_DEFAULTS))
+            if unknown:
+                raise TypeError(f"episodic_kwargs: unknown keys {unknown} ({', '.join(NGU_DEFAULTS)})")
+            self.ngu_mod_max = float(episodic.pop("mod_max", NGU_DEFAULTS["mod_max"]))
+            if not self.ngu_mod_max >= 1.0:
+                raise ValueError(f"episodic_kwargs: mod_max must be at least 1, not {self.ngu_mod_max}")
         super().__init__(buffer_size, n_envs, obs_space, action_space, gae_lam, gamma, device=device,
-                         obs_dtype=obs_dtype, draw_hash_matrix=draw_hash_matrix)
+                         obs_dtype=obs_dtype, draw_hash_matrix=draw_hash_matrix, hash_seed=hash_seed,
+                         episodic=episodic if do_ngu else None)
         self.int_gamma = int_gamma
         T, N = buffer_size, n_envs
         self.int_rewards = torch.zeros((T, N), device=self.device)
         self.int_values = torch.zeros((T, N), device=self.device)
         self.int_advantages = torch.zeros((T, N), device=self.device)
         self.int_returns = torch.zeros((T, N), device=self.device)
+        if do_ngu:
+            # running mean, variance and count of the lifelong error (RunningMeanStd's start); outlives reset()
+            self.em = torch.tensor([0.0, 1.0, 1e-4], dtype=torch.float64, device=self.device)
+            self.ngu_modulator = torch.zeros((T, N), device=self.device)
+            self.rnd_err = torch.zeros((T, N), device=self.device)
 
     def tensors(self):
         d = super().tensors()
@@ -321,10 +345,45 @@ class IntrinsicStorage(RolloutStorage):
         return d
 
     def add(self, obs, action, reward, int_reward, value, int_value, mask, log_prob):
+        """With the episodic state (PPO_NGU) `int_reward` is the raw lifelong error (None before it is trained):
+        int_rewards[t] is ngu()'s product and the rewards stay as given."""
         t = self.pos
-        self.int_rewards[t].copy_(_to_dev(int_reward, self.device).reshape(self.n_envs))
         self.int_values[t].copy_(_to_dev(int_value, self.device).reshape(self.n_envs))
+        if not self.do_episodic:
+            self.int_rewards[t].copy_(_to_dev(int_reward, self.device).reshape(self.n_envs))
+        elif int_reward is None:
+            self._add_err = None
+        else:
+            self._add_err = self.rnd_err[t]
+            self._add_err.copy_(_to_dev(int_reward, self.device).reshape(self.n_envs))
         super().add(obs, action, reward, value, mask, log_prob)
+
+    def _episodic_step(self, t):
+        self.ngu(self.obs_slots[t], self.masks[t], self._add_err, t)
+
+    def ngu(self, obs, dones, err, t=None):
+        """NGU's reward of one step, three launches on preallocated buffers with nothing read
+        back: the embedding and the k nearest of RolloutStorage.episodic, then the episodic bonus into
+        episodic_bonus[t], the modulator of the lifelong error `err` ((n_envs,) f32 on the device, or None: 1)
+        into ngu_modulator[t] and their product into int_rewards[t] (t: the step, default pos)."""
+        x = obs.reshape(self.n_envs, -1)
+        if x.dtype != torch.uint8 or x.stride(-1) != 1:
+            raise TypeError("ngu: this storage embeds uint8 observations with contiguous rows")
+        if err is not None and (err.dtype != torch.float32 or err.shape != (self.n_envs,) or not err.is_contiguous()
+                                or err.device != self.int_rewards.device):
+            raise TypeError("ngu: err must be a contiguous (n_envs,) float32 tensor on the storage's device")
+        if self.epi_offset:
+            x = x[:, self.epi_offset:]
+        N, K = self.n_envs, self.epi_k
+        t = self.pos if t is None else t
+        decay, _, eps, xi, c, smax = self.epi_coef
+        native.simhash_sums_u8(x, N, self.epi_D, x.stride(0), self.epi_A8, self.epi_rowsum, self.epi_workspace,
+                               self.epi_emb)
+        native.episodic_knn(self.epi_emb, dones, N, self.epi_capacity, K, self.mem, self.count, self.epi_dk,
+                            self.epi_kfound, self.epi_mk)
+        native.ngu_reward(self.epi_dk, self.epi_kfound, self.epi_mk, err, N, K, self.dm, self.em, decay, eps, xi, c,
+                          smax, self.ngu_mod_max, self.int_rewards[t], self.episodic_bonus[t], self.ngu_modulator[t])
+        return self.int_rewards[t]
 
     @traced("gae")
     def compute_returns_and_advantages(self, last_value, last_int_value, dones):

@@ -12,6 +12,8 @@
 //                           ring and lane 0 advances / resets the count.  No LDS, no scratch, no atomics.
 //   episodic_reward_kernel  one workgroup, all f64, contraction off (Makefile): the adjacent-pair tree sum of the
 //                           envs' mean distances, the running mean dm, and the reward formula per env.
+//   ngu_reward_kernel       PPO_NGU's (tests/ngu_twin.py) in place of the one above, from the same
+//                           __device__ pieces: that bonus times a modulator from the RND error's running moments.
 // The distances are integers, so any order of evaluation gives the same bits; the f64 sums are in a fixed order.
 #include <cmath>
 
@@ -132,6 +134,68 @@ __device__ inline double pair_tree(long long i0, long long len, F x) {
 // divides of 4 envs per thread are short next to a second launch
 constexpr int RT = 1024, RW = RT / 64;
 
+// the values per thread of the padded length: a power of two, at least one value per thread
+__device__ inline long long tree_per_thread(long long N) {
+    long long P = RT;
+    while (P < N) P <<= 1;
+    return P / RT;
+}
+
+// the tree over x(0 .. N) up to the wave: this thread's `per` consecutive values, then lane pairs, pairs of pairs
+// ... (the tree's next six levels); every lane returns its wave's sum
+template <typename F>
+__device__ inline double wave_tree(long long per, F x) {
+    double v = pair_tree(threadIdx.x * per, per, x);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v = v + __shfl_xor(v, o, 64);
+    return v;
+}
+
+// the tree's last levels, over the waves' sums (one thread; wsum is overwritten)
+__device__ inline double waves_tree(double* wsum) {
+    for (int s = 1; s < RW; s <<= 1)
+        for (int w = 0; w < RW; w += 2 * s) wsum[w] = wsum[w] + wsum[w + s];
+    return wsum[0];
+}
+
+// #{kfound > 0} among this wave's envs (every lane returns it)
+__device__ inline long long wave_valid_count(const int32_t* __restrict__ kfound, long long N, long long per) {
+    const long long tid = threadIdx.x;
+    long long cnt = 0;
+    for (long long i = tid * per; i < (tid + 1) * per && i < N; ++i) cnt += kfound[i] > 0;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) cnt += __shfl_xor(cnt, o, 64);
+    return cnt;
+}
+
+// the running mean of the squared kNN distance advanced by this step's tree sum S over nv valid envs (one thread)
+__device__ inline double dm_update(double* __restrict__ dm, double S, long long nv, double decay) {
+    double d0 = dm[0];
+    if (nv > 0) {
+        const double mu = S / (double)nv;
+        d0 = dm[1] == 0.0 ? mu : decay * d0 + (1.0 - decay) * mu;
+        dm[0] = d0;
+        dm[1] = dm[1] + 1.0;
+    }
+    return d0;
+}
+
+// env n's bonus from its k nearest and the updated dm[0]
+__device__ inline double episodic_r(const double* __restrict__ dk, const int32_t* __restrict__ kfound, long long n,
+                                    int K, double d0, double eps, double xi, double c, double smax) {
+    const int k = kfound[n] < K ? kfound[n] : K;  // (the knn kernel writes at most K)
+    if (k <= 0) return 0.0;
+    double acc = 0.0;
+    for (int i = 0; i < k; ++i) {
+        double q = d0 > 0.0 ? dk[n * K + i] / d0 : 0.0;
+        q = q - xi;
+        q = q > 0.0 ? q : 0.0;
+        acc = acc + eps / (q + eps);
+    }
+    const double s = sqrt(acc) + c;
+    return s > smax ? 0.0 : 1.0 / s;
+}
+
 __global__ void __launch_bounds__(RT)
     episodic_reward_kernel(const double* __restrict__ dk, const int32_t* __restrict__ kfound,
                            const double* __restrict__ mk, long long N, int K, double* __restrict__ dm, double decay,
@@ -141,17 +205,9 @@ __global__ void __launch_bounds__(RT)
     __shared__ long long wcnt[RW];
     __shared__ double dm0;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    long long P = RT;  // the padded length: a power of two, at least one value per thread
-    while (P < N) P <<= 1;
-    const long long per = P / RT;
-    long long cnt = 0;
-    for (long long i = tid * per; i < (tid + 1) * per && i < N; ++i) cnt += kfound[i] > 0;
-    double v = pair_tree(tid * per, per, [&](long long i) { return i < N && kfound[i] > 0 ? mk[i] : 0.0; });
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {  // lane pairs, then pairs of pairs: the tree's next six levels
-        v = v + __shfl_xor(v, o, 64);
-        cnt += __shfl_xor(cnt, o, 64);
-    }
+    const long long per = tree_per_thread(N);
+    const long long cnt = wave_valid_count(kfound, N, per);
+    const double v = wave_tree(per, [&](long long i) { return i < N && kfound[i] > 0 ? mk[i] : 0.0; });
     if (lane == 0) {
         wsum[wv] = v;
         wcnt[wv] = cnt;
@@ -160,36 +216,92 @@ __global__ void __launch_bounds__(RT)
     if (tid == 0) {
         long long nv = 0;
         for (int w = 0; w < RW; ++w) nv += wcnt[w];
-        for (int s = 1; s < RW; s <<= 1)  // the tree's last levels, over the waves
-            for (int w = 0; w < RW; w += 2 * s) wsum[w] = wsum[w] + wsum[w + s];
-        const double S = wsum[0];
-        double d0 = dm[0];
-        if (nv > 0) {
-            const double mu = S / (double)nv;
-            d0 = dm[1] == 0.0 ? mu : decay * d0 + (1.0 - decay) * mu;
-            dm[0] = d0;
-            dm[1] = dm[1] + 1.0;
-        }
-        dm0 = d0;
+        dm0 = dm_update(dm, waves_tree(wsum), nv, decay);
     }
     __syncthreads();
     const double d0 = dm0;
     for (long long n = tid; n < N; n += RT) {
-        const int k = kfound[n] < K ? kfound[n] : K;  // (the knn kernel writes at most K)
-        double r = 0.0;
-        if (k > 0) {
-            double acc = 0.0;
-            for (int i = 0; i < k; ++i) {
-                double q = d0 > 0.0 ? dk[n * K + i] / d0 : 0.0;
-                q = q - xi;
-                q = q > 0.0 ? q : 0.0;
-                acc = acc + eps / (q + eps);
-            }
-            const double s = sqrt(acc) + c;
-            r = s > smax ? 0.0 : 1.0 / s;
-        }
+        const double r = episodic_r(dk, kfound, n, K, d0, eps, xi, c, smax);
         bonus[n] = (float)r;
         rewards[n] = rewards[n] + (float)(beta * r);
+    }
+}
+
+// NGU's reward: the episodic r of the kernel above times a modulator from the lifelong (RND) error's
+// running moments.  Three tree sums, the third depending on the second's mean, so three rounds through the LDS:
+//   1  S (the kNN means) and sum(e) side by side            -> thread 0: dm, mb
+//   2  sum((e - mb)^2)                                      -> thread 0: the Chan merge into em
+//   3  per env r, the modulator and their product
+// err == nullptr (RND's warm-up): round 1 without e, no round 2, modulator 1, em neither read nor written.
+__global__ void __launch_bounds__(RT)
+    ngu_reward_kernel(const double* __restrict__ dk, const int32_t* __restrict__ kfound,
+                      const double* __restrict__ mk, const float* __restrict__ err, long long N, int K,
+                      double* __restrict__ dm, double* __restrict__ em, double decay, double eps, double xi, double c,
+                      double smax, double mod_max, float* __restrict__ int_rewards, float* __restrict__ bonus,
+                      float* __restrict__ modulator) {
+    __shared__ double wsum[RW], wsum_e[RW];
+    __shared__ long long wcnt[RW];
+    __shared__ double bc[3];  // dm[0]; mb, then em[0]; sigma
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const bool has_err = err != nullptr;  // uniform over the workgroup
+    const long long per = tree_per_thread(N);
+    const long long cnt = wave_valid_count(kfound, N, per);
+    const double v = wave_tree(per, [&](long long i) { return i < N && kfound[i] > 0 ? mk[i] : 0.0; });
+    double ve = 0.0;
+    if (has_err) ve = wave_tree(per, [&](long long i) { return i < N ? (double)err[i] : 0.0; });
+    if (lane == 0) {
+        wsum[wv] = v;
+        wsum_e[wv] = ve;
+        wcnt[wv] = cnt;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        long long nv = 0;
+        for (int w = 0; w < RW; ++w) nv += wcnt[w];
+        bc[0] = dm_update(dm, waves_tree(wsum), nv, decay);
+        if (has_err) bc[1] = waves_tree(wsum_e) / (double)N;
+    }
+    __syncthreads();
+    const double d0 = bc[0];
+    double mean = 0.0, sigma = 0.0;
+    if (has_err) {
+        const double mb = bc[1];
+        const double vv = wave_tree(per, [&](long long i) {
+            if (i >= N) return 0.0;
+            const double d = (double)err[i] - mb;
+            return d * d;
+        });
+        if (lane == 0) wsum_e[wv] = vv;  // (thread 0's reads of wsum_e lie before the barrier above)
+        __syncthreads();                 // ... and every thread has read mb: bc[1] is free
+        if (tid == 0) {
+            const double vb = waves_tree(wsum_e) / (double)N, n = (double)N;
+            const double m0 = em[0], v0 = em[1], c0 = em[2];
+            const double delta = mb - m0;
+            const double tot = c0 + n;
+            const double m1 = m0 + delta * n / tot;
+            const double M2 = v0 * c0 + vb * n + delta * delta * c0 * n / tot;
+            const double v1 = M2 / tot;
+            em[0] = m1;
+            em[1] = v1;
+            em[2] = tot;
+            bc[1] = m1;
+            bc[2] = sqrt(v1);
+        }
+        __syncthreads();
+        mean = bc[1];
+        sigma = bc[2];
+    }
+    for (long long n = tid; n < N; n += RT) {
+        const double r = episodic_r(dk, kfound, n, K, d0, eps, xi, c, smax);
+        double mod = 1.0;
+        if (has_err) {
+            const double a = sigma > 0.0 ? 1.0 + ((double)err[n] - mean) / sigma : 1.0;
+            mod = a > 1.0 ? a : 1.0;
+            mod = mod < mod_max ? mod : mod_max;
+        }
+        bonus[n] = (float)r;
+        modulator[n] = (float)mod;
+        int_rewards[n] = (float)(r * mod);
     }
 }
 
@@ -216,4 +328,18 @@ extern "C" int ppox_episodic_reward(const double* dk, const int32_t* kfound, con
     episodic_reward_kernel<<<1, RT, 0, ppox::as_stream(stream)>>>(dk, kfound, mk, N, K, dm, decay, beta, eps, xi, c,
                                                                    smax, rewards, bonus);
     PPOX_LAUNCHED("ppox_episodic_reward");
+}
+
+extern "C" int ppox_ngu_reward(const double* dk, const int32_t* kfound, const double* mk, const float* err, int64_t N,
+                               int32_t K, double* dm, double* em, double decay, double eps, double xi, double c,
+                               double smax, double mod_max, float* int_rewards, float* bonus, float* modulator,
+                               void* stream) {
+    PPOX_REQUIRE(dk && kfound && mk && dm && em && int_rewards && bonus && modulator,
+                 "ppox_ngu_reward: null pointer");
+    PPOX_REQUIRE(N >= 1 && N <= 0x7FFFFFFFll, "ppox_ngu_reward: N must lie in [1, 2^31), not %lld", (long long)N);
+    PPOX_REQUIRE(K >= 1 && K <= KMAX, "ppox_ngu_reward: K must lie in [1, 16], not %d", (int)K);
+    PPOX_REQUIRE(mod_max >= 1.0, "ppox_ngu_reward: mod_max must be at least 1, not %g", mod_max);
+    ngu_reward_kernel<<<1, RT, 0, ppox::as_stream(stream)>>>(dk, kfound, mk, err, N, K, dm, em, decay, eps, xi, c, smax,
+                                                             mod_max, int_rewards, bonus, modulator);
+    PPOX_LAUNCHED("ppox_ngu_reward");
 }

@@ -64,6 +64,8 @@ SIGNATURES = {
     "ppox_simhash_sums_u8": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
     "ppox_episodic_knn": [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "ppox_episodic_reward": [_vp, _vp, _vp, _i64, _i32, _vp, _f64, _f64, _f64, _f64, _f64, _f64, _vp, _vp, _vp],
+    "ppox_ngu_reward": [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _f64, _f64, _f64, _f64, _f64, _f64, _vp, _vp, _vp,
+                        _vp],
     "ppox_gather_rows": [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp],
     "ppox_grad_sumsq": [_vp, _i64, _vp, _vp],
     "ppox_adam_step": [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _f64, _f64, _f64, _f64, _i64, _vp, _vp],
@@ -482,6 +484,15 @@ def episodic_reward(dk, kfound, mk, N, K, dm, decay, beta, eps, xi, c, smax, rew
     written, rewards (N,) f32 += beta * bonus."""
     call("ppox_episodic_reward", _p(dk), _p(kfound), _p(mk), N, K, _p(dm), decay, beta, eps, xi, c, smax,
          _p(rewards), _p(bonus), stream_ptr(stream))
+
+
+def ngu_reward(dk, kfound, mk, err, N, K, dm, em, decay, eps, xi, c, smax, mod_max, int_rewards, bonus, modulator,
+               stream=None):
+    """NGU's reward of one step from episodic_knn's outputs and the lifelong error err (N,) f32 (None: modulator
+    1, em untouched): dm (2,) and em (3,) f64 advanced, bonus, modulator and int_rewards = bonus * modulator
+    (N,) f32 written.  include/ppox.h has the semantics."""
+    call("ppox_ngu_reward", _p(dk), _p(kfound), _p(mk), _p(err), N, K, _p(dm), _p(em), decay, eps, xi, c, smax,
+         mod_max, _p(int_rewards), _p(bonus), _p(modulator), stream_ptr(stream))
 
 
 def categorical_sample(logits, N, A, env_offset, seed, counter, actions, log_probs, stream=None):

@@ -13,7 +13,8 @@ object; default: the synthetic env for env_id), quiet, dynamics ("synthetic";
 KeyDoor-v0, whose visit-count table learn() logs as rollout/coverage), sil_kwargs (PPO(sil=True):
 size, alpha, beta, epochs, batch of the self-imitation module, sil_module.py), episodic / episodic_kwargs
 (PPO(episodic=True): a per-episode kNN novelty bonus on the uint8 frames; k, capacity, beta, eps,
-xi, c, smax, decay, frames).
+xi, c, smax, decay, frames).  PPO_NGU is PPO_RND with that bonus times an RND modulator as its
+intrinsic reward.
 
 Per iteration on each rank:
   collect: T x [net forward (rocBLAS + MFMA convs) -> ppox_categorical_sample ->
@@ -471,6 +472,8 @@ class BaseAlgorithm:
             # the rollout's mean bonus (before beta) and the running mean squared kNN distance (two host reads)
             logger.record("rollout/episodic_bonus", float(self.rollout.episodic_bonus.mean().item()))
             logger.record("rollout/episodic_dm", float(self.rollout.dm[0].item()))
+            if hasattr(self.rollout, "ngu_modulator"):
+                logger.record("rollout/ngu_modulator", float(self.rollout.ngu_modulator.mean().item()))
         if extra:
             for k, v in extra.items():
                 logger.record(k, v)
@@ -723,7 +726,8 @@ class PPO_RND(BaseAlgorithm):
         self.image = _is_image(self.env.observation_space)
         self.rnd_features = 84 * 84 if self.image else self.state_dim
         self.rnd = RndNetwork(self.rnd_features, hidden_size=int_hidden_size)
-        self.rollout = self._new_rollout(IntrinsicStorage, gae_lam=gae_lam, gamma=gamma, int_gamma=int_gamma)
+        self.rollout = self._new_rollout(IntrinsicStorage, gae_lam=gae_lam, gamma=gamma, int_gamma=int_gamma,
+                                         **self._rollout_kwargs())
         self.flat = FlatParams(self.policy.net, self.device)
         self._attach_convs()
         self.rnd_flat = FlatParams(self.rnd, self.device)
@@ -731,6 +735,12 @@ class PPO_RND(BaseAlgorithm):
         self.int_lr, self.rnd_start, self.int_vf_coef = int_lr, rnd_start, int_vf_coef
         self.int_rew_rms = RunningMeanStd(device=self.device)
         self._alloc_train_state()
+
+    int_adv_coef = 1.0  # the weight of the normalised intrinsic advantage in the loss (PPO_NGU sets it)
+
+    def _rollout_kwargs(self):
+        """Further keywords of this class's IntrinsicStorage (none here)."""
+        return {}
 
     def _rnd_input(self, obs):
         """(N, F) view of the features RND sees: last frame (image) or the obs vector (rows of
@@ -754,19 +764,24 @@ class PPO_RND(BaseAlgorithm):
             self.env.step_into(ro.obs_slots[t], ro.obs_slots[t + 1], ro.actions[t], ro.rewards[t], ro.masks[t],
                                ro.done_ret[t], ro.done_len[t])
             self.num_timesteps += self.num_envs
-            if (self.num_timesteps / self.num_envs) < self.rnd_start:        # ppo.py:390-392
-                ro.int_rewards[t].zero_()
-                self._update_obs_rms(self._rnd_input(ro.obs_slots[t]))
-            else:                                                              # ppo.py:394-398
-                with torch.no_grad():
-                    ir = self.rnd.int_reward(self.normalize_obs(self._rnd_input(ro.obs_slots[t + 1])))
-                self._scale_int_rewards(ir)
-                ro.int_rewards[t].copy_(ir)
+            self._int_reward_step(t)
         ro.pos, ro.full = self.nstep, True
         T1 = self.nstep - 1
         ro.compute_returns_and_advantages(ro.values[T1], ro.int_values[T1], ro.masks[T1])
         self._finish_episodes()
         return True
+
+    def _int_reward_step(self, t):
+        """int_rewards[t] of the collect loop, after step t's env step."""
+        ro = self.rollout
+        if (self.num_timesteps / self.num_envs) < self.rnd_start:            # ppo.py:390-392
+            ro.int_rewards[t].zero_()
+            self._update_obs_rms(self._rnd_input(ro.obs_slots[t]))
+        else:                                                                  # ppo.py:394-398
+            with torch.no_grad():
+                ir = self.rnd.int_reward(self.normalize_obs(self._rnd_input(ro.obs_slots[t + 1])))
+            self._scale_int_rewards(ir)
+            ro.int_rewards[t].copy_(ir)
 
     def _rnd_rows(self, ro, idx):
         """The minibatch rows RND trains on: on images only their last frame is gathered (7 KB
@@ -828,6 +843,10 @@ class PPO_RND(BaseAlgorithm):
         for _ in range(self.n_epochs):
             perm_dev, local, offs, sizes = self._epoch_minibatches(total)
             native.minibatch_adv_stats(adv, iadv, perm_dev, total, bs, self.nstep, self.num_envs, stats)
+            if self.int_adv_coef != 1.0:
+                # the loss kernels divide the centred intrinsic advantage by (std + 1e-8): this std makes that
+                # quotient int_adv_coef times the normalised advantage (one line on n_minibatches values)
+                stats[:, 3].add_(1e-8).div_(self.int_adv_coef).sub_(1e-8)
             for k, B in enumerate(sizes):
                 idx = local[offs[k]:offs[k + 1]]
                 Bl = idx.numel()
@@ -862,6 +881,52 @@ class PPO_RND(BaseAlgorithm):
 
     def learn(self, total_timesteps, log_interval, reward_target=None, log_to_file=False):
         return self._learn("RND", total_timesteps, log_interval, reward_target, log_to_file)
+
+
+class PPO_NGU(PPO_RND):
+    """Never Give Up's reward on PPO_RND's two value streams (an extension of this project): the
+    per-episode kNN bonus of PPO(episodic=True) times a modulator in [1, mod_max] from the RND error's running
+    moments, paid as the intrinsic reward (own value head, non-episodic return, separately normalised advantage)
+    while the rewards stay the env's own.  PPO_RND's keywords plus episodic_kwargs (k, capacity, eps, xi, c, smax,
+    decay, frames, mod_max: buffer.NGU_DEFAULTS; capacity defaults to the env's max_len where it has one) and
+    int_adv_coef, the weight of the normalised intrinsic advantage in the loss.
+
+    Both bonuses of step t are of obs_slots[t], the observation the action was taken in (PPO(episodic=True)'s
+    convention); PPO_RND scores obs_slots[t + 1].  The product is bounded by mod_max / c, so there is no
+    int_rew_rms scaling.  NGU's learned embedding, its family of (beta, gamma) pairs and its recurrent agent are
+    not part of this."""
+
+    def __init__(self, *, episodic_kwargs=None, int_adv_coef=1.0, **kw):
+        if DistContext.current().enabled:
+            raise NotImplementedError("PPO_NGU under a process group: the running moments of the kNN distance (dm) "
+                                      "and of the RND error (em) are not reduced over ranks")
+        if not float(int_adv_coef) > 0.0:
+            raise ValueError(f"int_adv_coef must be positive, not {int_adv_coef}")
+        self._ngu_kwargs = dict(episodic_kwargs or {})
+        super().__init__(**kw)
+        self.int_adv_coef = float(int_adv_coef)
+
+    def _rollout_kwargs(self):
+        cfg = dict(self._ngu_kwargs)
+        max_len = getattr(self.env, "max_len", None)
+        if "capacity" not in cfg and max_len is not None:
+            cfg["capacity"] = int(max_len)
+        return {"episodic": cfg, "hash_seed": self.seed}
+
+    def _int_reward_step(self, t):
+        """PPO_RND's eager collect loop with this step in place of its own: sums -> knn -> ngu_reward on
+        obs_slots[t], nothing read back."""
+        ro = self.rollout
+        if (self.num_timesteps / self.num_envs) < self.rnd_start:            # RND's warm-up: modulator 1
+            self._update_obs_rms(self._rnd_input(ro.obs_slots[t]))
+            ro.ngu(ro.obs_slots[t], ro.masks[t], None, t)
+        else:
+            with torch.no_grad():
+                ro.rnd_err[t].copy_(self.rnd.int_reward(self.normalize_obs(self._rnd_input(ro.obs_slots[t]))))
+            ro.ngu(ro.obs_slots[t], ro.masks[t], ro.rnd_err[t], t)
+
+    def learn(self, total_timesteps, log_interval, reward_target=None, log_to_file=False):
+        return self._learn("PPO_NGU", total_timesteps, log_interval, reward_target, log_to_file)
 
 
 class PPO_ICM(BaseAlgorithm):

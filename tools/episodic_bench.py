@@ -4,11 +4,13 @@
    each alone and the three together, single launches after warm-up: once early in the episode (8 embeddings in every
    memory) and once with full memories (count = capacity), for both `frames` settings; beside them the pixel-hash keys
    (ppox_simhash_keys_u8 on the whole stack) and one env step on the same frames, the yardsticks of §4.3 / §11.
+   Beside ppox_episodic_reward, on the same kNN outputs: ppox_ngu_reward (PPO_NGU) with the lifelong
+   error and without it (RND's warm-up).
 2. One learn() iteration (collect_samples + train at --n-envs x --nstep, --batch-size, --n-epochs) of PPO(episodic=True)
    against the default PPO, each in this process after --warmup iterations (the first collect is eager and captures
    the graph), host wall time around a device synchronize.
 
-    python tools/episodic_bench.py [--out profiles/episodic/step_time.json]
+    python tools/episodic_bench.py [--out profiles/episodic/step_time.json] [--no-iterations]
 """
 import argparse
 import json
@@ -54,6 +56,10 @@ def step_times(args):
     never = torch.zeros(n, dtype=torch.uint8, device=d)
     dret, dlen = torch.empty(n, device=d), torch.empty(n, dtype=torch.int32, device=d)
     res = {}
+    # ppox_ngu_reward's own arguments: lognormal errors, the running moments, the three outputs
+    err = torch.randn(n, device=d).mul_(2.0).exp_()
+    em = torch.tensor([0.0, 1.0, 1e-4], dtype=torch.float64, device=d)
+    ngu_out = torch.zeros((3, n), device=d)
     for frames in ("last", "stack"):
         st = buffer.RolloutStorage(1, n, env.observation_space, env.action_space,
                                    episodic=dict(capacity=args.capacity, frames=frames))
@@ -65,6 +71,9 @@ def step_times(args):
                                           st.epi_kfound, st.epi_mk)
         rew = lambda: native.episodic_reward(st.epi_dk, st.epi_kfound, st.epi_mk, n, K, st.dm, *st.epi_coef,  # noqa: E731
                                              rewards, st.episodic_bonus[0])
+        decay, _, eps, xi, c, smax = st.epi_coef
+        ngu = lambda e: native.ngu_reward(st.epi_dk, st.epi_kfound, st.epi_mk, e, n, K, st.dm, em, decay,  # noqa: E731
+                                          eps, xi, c, smax, 5.0, ngu_out[0], ngu_out[1], ngu_out[2])
         # memories of random-walk embeddings: 8 rows, then all of them (the timed knn launches keep appending, so
         # the count is put back before each phase; a full ring stays full)
         for j in range(L):
@@ -78,6 +87,8 @@ def step_times(args):
                 "sums": timed(sums, args.launches, args.warmup),
                 "knn": timed(knn, args.launches, args.warmup, before=put_back),
                 "reward": timed(rew, args.launches, args.warmup),
+                "ngu_reward": timed(lambda: ngu(err), args.launches, args.warmup),
+                "ngu_reward_no_err": timed(lambda: ngu(None), args.launches, args.warmup),
                 "three_launches": timed(lambda: st.episodic(obs[0], rewards, never, 0), args.launches, args.warmup,
                                         before=put_back)}
         del st
@@ -135,10 +146,13 @@ def main():
     ap.add_argument("--n-epochs", type=int, default=4)
     ap.add_argument("--iterations", type=int, default=3)
     ap.add_argument("--iter-warmup", type=int, default=2)
+    ap.add_argument("--no-iterations", action="store_true", help="the step's launches only")
     ap.add_argument("--out", default=os.path.join("profiles", "episodic", "step_time.json"))
     args = ap.parse_args()
     out = {"device": torch.cuda.get_device_name(0), "config": {k: v for k, v in vars(args).items() if k != "out"},
-           "step": step_times(args), "learn_iteration": iteration_times(args)}
+           "step": step_times(args)}
+    if not args.no_iterations:
+        out["learn_iteration"] = iteration_times(args)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)

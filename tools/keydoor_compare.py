@@ -1,5 +1,5 @@
-"""PPO, PPO(sim_hash=True), PPO_RND, PPO_ICM and PPO(episodic=True) on KeyDoor-v0 for a fixed number of env steps and
-three seeds. Every run is a fresh child process under its own `timeout`; its log points (env steps,
+"""PPO, PPO(sim_hash=True), PPO_RND, PPO_ICM, PPO(episodic=True) and PPO_NGU (defaults, and int_adv_coef=0.3) on
+KeyDoor-v0 for a fixed number of env steps and three seeds. Every run is a fresh child process under its own `timeout`; its log points (env steps,
 ep_rew_mean — the mean return of the last 50 episodes, which on this task is the goal rate —, coverage) go as one
 JSON line each into --out, after one line per seed with the numpy twin's random-policy goal rate at that seed and
 max_len (tests/keydoor_twin.py, CPU: the reference the learning gate is measured against).  The tool stops at the
@@ -21,6 +21,8 @@ CONFIGS = {
     "PPO_RND": ("PPO_RND", {}),
     "PPO_ICM": ("PPO_ICM", {}),
     "PPO_Episodic": ("PPO", {"episodic": True}),  # the defaults: k 10, capacity max_len, the newest frame
+    "PPO_NGU": ("PPO_NGU", {}),                   # the same episodic defaults, mod_max 5, int_adv_coef 1
+    "PPO_NGU_0.3": ("PPO_NGU", {"int_adv_coef": 0.3}),
 }
 
 
@@ -49,11 +51,13 @@ def child(args):
                "coverage": kv["rollout/coverage"], "seconds": round(time.time() - t0, 2)}
         if "rollout/episodic_bonus" in kv:
             row.update(episodic_bonus=kv["rollout/episodic_bonus"], episodic_dm=kv["rollout/episodic_dm"])
+        if "rollout/ngu_modulator" in kv:
+            row.update(ngu_modulator=kv["rollout/ngu_modulator"], mean_int_reward=kv["rollout/mean_int_reward"])
         print(json.dumps(row), flush=True)
         real_dump(step)
 
     logger.dump = dump
-    alg.learn(total_timesteps=args.steps, log_interval=1)
+    alg.learn(total_timesteps=args.steps, log_interval=args.log_interval)
     torch.cuda.synchronize()
 
 
@@ -70,6 +74,7 @@ def main():
     ap.add_argument("--batch-size", type=int, default=2048)
     ap.add_argument("--n-epochs", type=int, default=4)
     ap.add_argument("--lr", type=float, default=5e-4)
+    ap.add_argument("--log-interval", type=int, default=1, help="iterations between log points")
     ap.add_argument("--timeout", type=int, default=120, help="seconds per child")
     ap.add_argument("--out", default=os.path.join("profiles", "keydoor", "compare.jsonl"))
     args = ap.parse_args()
@@ -80,7 +85,7 @@ def main():
     import keydoor_twin as K
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     shared = ["--steps", args.steps, "--max-len", args.max_len, "--n-envs", args.n_envs, "--nstep", args.nstep,
-              "--batch-size", args.batch_size, "--n-epochs", args.n_epochs, "--lr", args.lr]
+              "--batch-size", args.batch_size, "--n-epochs", args.n_epochs, "--lr", args.lr, "--log-interval", args.log_interval]
     with open(args.out, "w") as out:
         def emit(line):
             out.write(line.rstrip("\n") + "\n")
