@@ -250,6 +250,33 @@ int ppox_ngu_reward(const double* dk, const int32_t* kfound, const double* mk, c
                     int64_t N, int32_t K, double* dm, double* em, double decay, double eps,
                     double xi, double c, double smax, double mod_max, float* int_rewards,
                     float* bonus, float* modulator, void* stream);
+/* Elliptical episodic bonus (E3B; PPO(episodic=True, episodic_kwargs={"kind": "elliptical"});
+ * DESIGN.md §4.7, parity to tests/elliptical_twin.py) on the same embeddings, in place of
+ * ppox_episodic_knn + ppox_episodic_reward: b = phi' M phi with M = (ridge I + sum of this
+ * episode's phi phi')^-1, advanced by a rank-one Sherman-Morrison update.  State: minv
+ * (N, 16, 16) f64 row-major = M, starts at diag(1 / ridge); count (N,) int32, steps so far in
+ * the episode.  Per env n, all f64, every operation rounded on its own, sums in the stated
+ * order from +0.0: phi_i = (double)emb[n][i]; u_i = sum_{j ascending} M[i][j] * phi_j;
+ * b_raw = sum_{i ascending} phi_i * u_i; b = b_raw > 0 ? b_raw : 0 (a NaN gives 0);
+ * den = 1 + b; M[i][j] = M[i][j] - (u_i * u_j) / den (product, divide, subtract: a symmetric M
+ * stays bitwise symmetric).  pay = count[n] > 0 ? b : 0 (an episode's first state is scored
+ * against nothing); eb[n] = pay; bonus != NULL: bonus[n] = (float)pay; rewards != NULL:
+ * rewards[n] = rewards[n] + (float)(beta * pay), one f32 add.  Then, where done[n] != 0:
+ * M = diag(1.0 / ridge) with +0.0 elsewhere and count[n] = 0 (the state that ended the episode
+ * was scored against that episode's M); else count[n] += 1, not past INT32_MAX.
+ * Refused with PPOX_EINVAL before any HIP call: a null emb, done, minv, count or eb, N outside
+ * [1, 2^31), ridge not finite or not > 0, beta not finite. */
+int ppox_elliptical_bonus(const int32_t* emb, const uint8_t* done, int64_t N, double ridge,
+                          double beta, double* minv, int32_t* count, double* eb, float* rewards,
+                          float* bonus, void* stream);
+/* The modulator half of ppox_ngu_reward for a bonus that is already computed (eb (N,) f64,
+ * ppox_elliptical_bonus's): mb, vb, the merge into em, sigma and mod_n exactly as stated
+ * there (err == NULL: mod_n = 1, em neither read nor written); with r = eb[n]:
+ * bonus[n] = (float)r; modulator[n] = (float)mod_n; int_rewards[n] = (float)(r * mod_n).
+ * One workgroup.  Refused with PPOX_EINVAL before any HIP call: a null pointer other than err,
+ * N outside [1, 2^31), mod_max < 1. */
+int ppox_ngu_modulate(const double* eb, const float* err, int64_t N, double* em, double mod_max,
+                      float* int_rewards, float* bonus, float* modulator, void* stream);
 
 /* ---------------------------------------------------------------------------
  * K5  Minibatch gather (buffer.py:41-52, 256-267): dst[r] = rollout row of the

@@ -48,6 +48,34 @@ EPISODIC_DEFAULTS = {"k": 10, "capacity": 256, "beta": 0.1, "eps": 1e-3, "xi": 8
 # PPO_NGU's episodic_kwargs: the bonus is not added to the rewards (no beta) and is multiplied by a modulator in
 # [1, mod_max] (NGU's L)
 NGU_DEFAULTS = dict({k: v for k, v in EPISODIC_DEFAULTS.items() if k != "beta"}, mod_max=5.0)
+# episodic_kwargs["kind"]: "knn" (the two dicts above) or "elliptical" (DESIGN.md §4.7), whose keys are these;
+# ridge is in the embedding's units (squared integer sums).  PPO_NGU: ridge, frames, mod_max (no beta, as above)
+EPISODIC_KINDS = ("knn", "elliptical")
+ELLIPTICAL_DEFAULTS = {"ridge": 2.0 ** 30, "beta": 0.1, "frames": "last"}
+NGU_ELLIPTICAL_KEYS = ("ridge", "frames", "mod_max")
+
+
+def pop_episodic_kind(kw):
+    """Takes "kind" out of the episodic_kwargs dict `kw` (before any other key is looked at) and returns it."""
+    kind = kw.pop("kind", "knn")
+    if kind not in EPISODIC_KINDS:
+        raise ValueError(f"episodic_kwargs: kind must be one of {', '.join(map(repr, EPISODIC_KINDS))}, not {kind!r}")
+    return kind
+
+
+def elliptical_config(kw, allowed=tuple(ELLIPTICAL_DEFAULTS)):
+    """kind="elliptical"'s episodic_kwargs `kw` (without "kind") checked against the `allowed` keys ->
+    ELLIPTICAL_DEFAULTS overridden by them."""
+    unknown = sorted(set(kw) - set(allowed))
+    if unknown:
+        raise TypeError(f"episodic_kwargs: unknown keys {unknown} for kind='elliptical' ({', '.join(allowed)})")
+    cfg = dict(ELLIPTICAL_DEFAULTS, **{k: v for k, v in kw.items() if k in ELLIPTICAL_DEFAULTS})
+    ridge = float(cfg["ridge"])
+    if not (np.isfinite(ridge) and ridge > 0.0):
+        raise ValueError(f"episodic_kwargs: ridge must be finite and positive, not {cfg['ridge']}")
+    if not np.isfinite(float(cfg["beta"])):
+        raise ValueError(f"episodic_kwargs: beta must be finite, not {cfg['beta']}")
+    return cfg
 
 
 class BaseBuffer:
@@ -136,20 +164,27 @@ class RolloutStorage(BaseBuffer):
 
     def _init_episodic(self, kw, seed):
         """The episodic bonus's state (`episodic`: a dict of EPISODIC_DEFAULTS' keys, or
-        True for the defaults).  It outlives reset(): episodes span rollouts."""
+        True for the defaults; with "kind": "elliptical", of ELLIPTICAL_DEFAULTS' keys: DESIGN.md §4.7).  It
+        outlives reset(): episodes span rollouts."""
         if self.obs_dtype != torch.uint8:
             raise NotImplementedError("episodic=True embeds uint8 observations through the int8 hash matrix; got "
                                       f"{self.obs_dtype} observations of shape {self.obs_shape}")
         if self.do_hash:
             raise NotImplementedError("episodic=True with sim_hash=True: two bonuses written into the same rewards "
                                       "are not implemented")
-        unknown = sorted(set(kw) - set(EPISODIC_DEFAULTS))
-        if unknown:
-            raise TypeError(f"episodic_kwargs: unknown keys {unknown} ({', '.join(EPISODIC_DEFAULTS)})")
-        cfg = dict(EPISODIC_DEFAULTS, **kw)
-        K, L, frames = int(cfg["k"]), int(cfg["capacity"]), cfg["frames"]
-        if not 1 <= K <= 16 or L < 1:
-            raise ValueError(f"episodic_kwargs: k must lie in [1, 16] and capacity be positive (k {K}, capacity {L})")
+        self.epi_kind = pop_episodic_kind(kw)
+        if self.epi_kind == "elliptical":
+            cfg = elliptical_config(kw)
+        else:
+            unknown = sorted(set(kw) - set(EPISODIC_DEFAULTS))
+            if unknown:
+                raise TypeError(f"episodic_kwargs: unknown keys {unknown} ({', '.join(EPISODIC_DEFAULTS)})")
+            cfg = dict(EPISODIC_DEFAULTS, **kw)
+            K, L = int(cfg["k"]), int(cfg["capacity"])
+            if not 1 <= K <= 16 or L < 1:
+                raise ValueError(f"episodic_kwargs: k must lie in [1, 16] and capacity be positive (k {K}, "
+                                 f"capacity {L})")
+        frames = cfg["frames"]
         if frames == "last":
             if len(self.obs_shape) != 3:
                 raise ValueError(f"episodic_kwargs: frames='last' needs (frames, H, W) observations, not "
@@ -161,20 +196,28 @@ class RolloutStorage(BaseBuffer):
         else:
             raise ValueError(f"episodic_kwargs: frames must be 'last' or 'stack', not {frames!r}")
         T, N, d = self.buffer_size, self.n_envs, self.device
-        self.epi_k, self.epi_capacity, self.epi_frames, self.epi_D = K, L, frames, D
-        self.epi_coef = tuple(float(cfg[x]) for x in ("decay", "beta", "eps", "xi", "c", "smax"))
+        self.epi_frames, self.epi_D = frames, D
         self.epi_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.epi_A8 = torch.empty((16, D), dtype=torch.int8, device=d)
         self.epi_rowsum = torch.empty(16, dtype=torch.int32, device=d)
         native.simhash_matrix_i8(D, self.epi_seed, self.epi_A8, self.epi_rowsum)
         self.epi_workspace = torch.empty(native.simhash_keys_u8_workspace_bytes(N) // 4, dtype=torch.int32, device=d)
         self.epi_emb = torch.zeros((N, 16), dtype=torch.int32, device=d)
-        self.mem = torch.zeros((N, L, 16), dtype=torch.int32, device=d)
         self.count = torch.zeros(N, dtype=torch.int32, device=d)
-        self.dm = torch.zeros(2, dtype=torch.float64, device=d)
-        self.epi_dk = torch.zeros((N, K), dtype=torch.float64, device=d)
-        self.epi_kfound = torch.zeros(N, dtype=torch.int32, device=d)
-        self.epi_mk = torch.zeros(N, dtype=torch.float64, device=d)
+        if self.epi_kind == "elliptical":
+            # C^-1 per env, at its start diag(1 / ridge), and the step's bonus in f64 (what ngu() modulates)
+            self.epi_ridge, self.epi_beta = float(cfg["ridge"]), float(cfg["beta"])
+            self.minv = torch.zeros((N, 16, 16), dtype=torch.float64, device=d)
+            self.minv.diagonal(dim1=1, dim2=2).fill_(1.0 / self.epi_ridge)
+            self.eb = torch.zeros(N, dtype=torch.float64, device=d)
+        else:
+            self.epi_k, self.epi_capacity = K, L
+            self.epi_coef = tuple(float(cfg[x]) for x in ("decay", "beta", "eps", "xi", "c", "smax"))
+            self.mem = torch.zeros((N, L, 16), dtype=torch.int32, device=d)
+            self.dm = torch.zeros(2, dtype=torch.float64, device=d)
+            self.epi_dk = torch.zeros((N, K), dtype=torch.float64, device=d)
+            self.epi_kfound = torch.zeros(N, dtype=torch.int32, device=d)
+            self.epi_mk = torch.zeros(N, dtype=torch.float64, device=d)
         # this rollout's bonus before beta, row t written by the step on obs_slots[t]
         self.episodic_bonus = torch.zeros((T, N), device=d)
 
@@ -249,15 +292,23 @@ class RolloutStorage(BaseBuffer):
         (graph-capturable): the integer embedding of `obs` (uint8 frames read in place, the newest frame or
         the whole stack) -> the k nearest of the env's episode so far, then the embedding appended and the
         memory emptied where `dones` (uint8) is set -> the bonus into episodic_bonus[t] (t: the step, default
-        pos) and beta times it added to `rewards` (this rank's (n_envs,) f32 row, mutated and returned)."""
+        pos) and beta times it added to `rewards` (this rank's (n_envs,) f32 row, mutated and returned).
+        kind="elliptical" (DESIGN.md §4.7): two launches, the embedding -> the elliptical bonus, minv's update and
+        the reward add in one kernel."""
         x = obs.reshape(self.n_envs, -1)
         if x.dtype != torch.uint8 or x.stride(-1) != 1:
             raise TypeError("episodic: this storage embeds uint8 observations with contiguous rows")
         if self.epi_offset:
             x = x[:, self.epi_offset:]
-        N, K = self.n_envs, self.epi_k
+        N = self.n_envs
         native.simhash_sums_u8(x, N, self.epi_D, x.stride(0), self.epi_A8, self.epi_rowsum, self.epi_workspace,
                                self.epi_emb)
+        if self.epi_kind == "elliptical":
+            # kind="elliptical" (DESIGN.md §4.7): one launch for the bonus, the state's update and the reward add
+            native.elliptical_bonus(self.epi_emb, dones, N, self.epi_ridge, self.epi_beta, self.minv, self.count,
+                                    self.eb, rewards, self.episodic_bonus[self.pos if t is None else t])
+            return rewards
+        K = self.epi_k
         native.episodic_knn(self.epi_emb, dones, N, self.epi_capacity, K, self.mem, self.count, self.epi_dk,
                             self.epi_kfound, self.epi_mk)
         native.episodic_reward(self.epi_dk, self.epi_kfound, self.epi_mk, N, K, self.dm, *self.epi_coef, rewards,
@@ -318,12 +369,17 @@ class IntrinsicStorage(RolloutStorage):
             # PPO_NGU: the episodic state of RolloutStorage, its bonus multiplied by a modulator
             # and written to the intrinsic stream instead of being added to the rewards
             episodic = dict(episodic) if isinstance(episodic, dict) else {}
-            unknown = sorted(set(episodic) - set(NGU_DEFAULTS))
-            if unknown:
-                raise TypeError(f"episodic_kwargs: unknown keys {unknown} ({', '.join(NGU_DEFAULTS)})")
+            kind = pop_episodic_kind(episodic)
+            if kind == "elliptical":
+                elliptical_config(episodic, NGU_ELLIPTICAL_KEYS)
+            else:
+                unknown = sorted(set(episodic) - set(NGU_DEFAULTS))
+                if unknown:
+                    raise TypeError(f"episodic_kwargs: unknown keys {unknown} ({', '.join(NGU_DEFAULTS)})")
             self.ngu_mod_max = float(episodic.pop("mod_max", NGU_DEFAULTS["mod_max"]))
             if not self.ngu_mod_max >= 1.0:
                 raise ValueError(f"episodic_kwargs: mod_max must be at least 1, not {self.ngu_mod_max}")
+            episodic["kind"] = kind
         super().__init__(buffer_size, n_envs, obs_space, action_space, gae_lam, gamma, device=device,
                          obs_dtype=obs_dtype, draw_hash_matrix=draw_hash_matrix, hash_seed=hash_seed,
                          episodic=episodic if do_ngu else None)
@@ -365,7 +421,8 @@ class IntrinsicStorage(RolloutStorage):
         """NGU's reward of one step, three launches on preallocated buffers with nothing read
         back: the embedding and the k nearest of RolloutStorage.episodic, then the episodic bonus into
         episodic_bonus[t], the modulator of the lifelong error `err` ((n_envs,) f32 on the device, or None: 1)
-        into ngu_modulator[t] and their product into int_rewards[t] (t: the step, default pos)."""
+        into ngu_modulator[t] and their product into int_rewards[t] (t: the step, default pos).
+        kind="elliptical" (DESIGN.md §4.7): sums -> elliptical_bonus (paid nowhere) -> ngu_modulate."""
         x = obs.reshape(self.n_envs, -1)
         if x.dtype != torch.uint8 or x.stride(-1) != 1:
             raise TypeError("ngu: this storage embeds uint8 observations with contiguous rows")
@@ -374,11 +431,18 @@ class IntrinsicStorage(RolloutStorage):
             raise TypeError("ngu: err must be a contiguous (n_envs,) float32 tensor on the storage's device")
         if self.epi_offset:
             x = x[:, self.epi_offset:]
-        N, K = self.n_envs, self.epi_k
+        N = self.n_envs
         t = self.pos if t is None else t
-        decay, _, eps, xi, c, smax = self.epi_coef
         native.simhash_sums_u8(x, N, self.epi_D, x.stride(0), self.epi_A8, self.epi_rowsum, self.epi_workspace,
                                self.epi_emb)
+        if self.epi_kind == "elliptical":
+            # kind="elliptical" (DESIGN.md §4.7): the bonus in f64, paid nowhere, then the modulator half alone
+            native.elliptical_bonus(self.epi_emb, dones, N, self.epi_ridge, 0.0, self.minv, self.count, self.eb)
+            native.ngu_modulate(self.eb, err, N, self.em, self.ngu_mod_max, self.int_rewards[t],
+                                self.episodic_bonus[t], self.ngu_modulator[t])
+            return self.int_rewards[t]
+        K = self.epi_k
+        decay, _, eps, xi, c, smax = self.epi_coef
         native.episodic_knn(self.epi_emb, dones, N, self.epi_capacity, K, self.mem, self.count, self.epi_dk,
                             self.epi_kfound, self.epi_mk)
         native.ngu_reward(self.epi_dk, self.epi_kfound, self.epi_mk, err, N, K, self.dm, self.em, decay, eps, xi, c,

@@ -14,6 +14,9 @@
 //                           envs' mean distances, the running mean dm, and the reward formula per env.
 //   ngu_reward_kernel       PPO_NGU's (tests/ngu_twin.py) in place of the one above, from the same
 //                           __device__ pieces: that bonus times a modulator from the RND error's running moments.
+//   elliptical_kernel       kind="elliptical" (tests/elliptical_twin.py) in place of the first two:
+//                           b = phi' C^-1 phi and the rank-one update of C^-1, 16 lanes per env; and
+//   ngu_modulate_kernel     ngu_reward_kernel's modulator half on that bonus.
 // The distances are integers, so any order of evaluation gives the same bits; the f64 sums are in a fixed order.
 #include <cmath>
 
@@ -227,6 +230,29 @@ __global__ void __launch_bounds__(RT)
     }
 }
 
+// Chan's merge of the batch moments (mb, vb, n) into em = (mean, variance, count), left to right as written
+// (util.py:30-44); out = the updated mean and sigma (one thread)
+__device__ inline void chan_merge(double* __restrict__ em, double mb, double vb, double n, double* out) {
+    const double m0 = em[0], v0 = em[1], c0 = em[2];
+    const double delta = mb - m0;
+    const double tot = c0 + n;
+    const double m1 = m0 + delta * n / tot;
+    const double M2 = v0 * c0 + vb * n + delta * delta * c0 * n / tot;
+    const double v1 = M2 / tot;
+    em[0] = m1;
+    em[1] = v1;
+    em[2] = tot;
+    out[0] = m1;
+    out[1] = sqrt(v1);
+}
+
+// the modulator of the error e against the updated moments, in [1, mod_max]
+__device__ inline double ngu_mod(double e, double mean, double sigma, double mod_max) {
+    const double a = sigma > 0.0 ? 1.0 + (e - mean) / sigma : 1.0;
+    const double mod = a > 1.0 ? a : 1.0;
+    return mod < mod_max ? mod : mod_max;
+}
+
 // NGU's reward: the episodic r of the kernel above times a modulator from the lifelong (RND) error's
 // running moments.  Three tree sums, the third depending on the second's mean, so three rounds through the LDS:
 //   1  S (the kNN means) and sum(e) side by side            -> thread 0: dm, mb
@@ -273,35 +299,151 @@ __global__ void __launch_bounds__(RT)
         });
         if (lane == 0) wsum_e[wv] = vv;  // (thread 0's reads of wsum_e lie before the barrier above)
         __syncthreads();                 // ... and every thread has read mb: bc[1] is free
-        if (tid == 0) {
-            const double vb = waves_tree(wsum_e) / (double)N, n = (double)N;
-            const double m0 = em[0], v0 = em[1], c0 = em[2];
-            const double delta = mb - m0;
-            const double tot = c0 + n;
-            const double m1 = m0 + delta * n / tot;
-            const double M2 = v0 * c0 + vb * n + delta * delta * c0 * n / tot;
-            const double v1 = M2 / tot;
-            em[0] = m1;
-            em[1] = v1;
-            em[2] = tot;
-            bc[1] = m1;
-            bc[2] = sqrt(v1);
-        }
+        if (tid == 0) chan_merge(em, mb, waves_tree(wsum_e) / (double)N, (double)N, bc + 1);
         __syncthreads();
         mean = bc[1];
         sigma = bc[2];
     }
     for (long long n = tid; n < N; n += RT) {
         const double r = episodic_r(dk, kfound, n, K, d0, eps, xi, c, smax);
-        double mod = 1.0;
-        if (has_err) {
-            const double a = sigma > 0.0 ? 1.0 + ((double)err[n] - mean) / sigma : 1.0;
-            mod = a > 1.0 ? a : 1.0;
-            mod = mod < mod_max ? mod : mod_max;
-        }
+        const double mod = has_err ? ngu_mod((double)err[n], mean, sigma, mod_max) : 1.0;
         bonus[n] = (float)r;
         modulator[n] = (float)mod;
         int_rewards[n] = (float)(r * mod);
+    }
+}
+
+// The modulator half of the kernel above for a bonus that is already there (eb, ppox_elliptical_bonus's; DESIGN.md
+// §4.7): rounds 1 and 2 on the error alone, then per env r = eb[n] in place of episodic_r.
+__global__ void __launch_bounds__(RT)
+    ngu_modulate_kernel(const double* __restrict__ eb, const float* __restrict__ err, long long N,
+                        double* __restrict__ em, double mod_max, float* __restrict__ int_rewards,
+                        float* __restrict__ bonus, float* __restrict__ modulator) {
+    __shared__ double wsum_e[RW];
+    __shared__ double bc[3];  // -; mb, then em[0]; sigma
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const bool has_err = err != nullptr;  // uniform over the workgroup
+    double mean = 0.0, sigma = 0.0;
+    if (has_err) {
+        const long long per = tree_per_thread(N);
+        const double ve = wave_tree(per, [&](long long i) { return i < N ? (double)err[i] : 0.0; });
+        if (lane == 0) wsum_e[wv] = ve;
+        __syncthreads();
+        if (tid == 0) bc[1] = waves_tree(wsum_e) / (double)N;
+        __syncthreads();
+        const double mb = bc[1];
+        const double vv = wave_tree(per, [&](long long i) {
+            if (i >= N) return 0.0;
+            const double d = (double)err[i] - mb;
+            return d * d;
+        });
+        if (lane == 0) wsum_e[wv] = vv;  // (thread 0's reads of wsum_e lie before the barrier above)
+        __syncthreads();                 // ... and every thread has read mb: bc[1] is free
+        if (tid == 0) chan_merge(em, mb, waves_tree(wsum_e) / (double)N, (double)N, bc + 1);
+        __syncthreads();
+        mean = bc[1];
+        sigma = bc[2];
+    }
+    for (long long n = tid; n < N; n += RT) {
+        const double r = eb[n];
+        const double mod = has_err ? ngu_mod((double)err[n], mean, sigma, mod_max) : 1.0;
+        bonus[n] = (float)r;
+        modulator[n] = (float)mod;
+        int_rewards[n] = (float)(r * mod);
+    }
+}
+
+// Elliptical episodic bonus (tests/elliptical_twin.py): b = phi' M phi with M = (ridge I + sum of
+// this episode's phi phi')^-1 kept per env as 16 x 16 f64 and advanced by a rank-one Sherman-Morrison update.
+// 16 lanes per env, four envs per wave, 16 envs per 256-thread block.  Lane i of a group holds row i of M in 16
+// f64 registers, forms u_i = sum_j M[i][j] phi_j in-lane, fetches the group's 16 u_j by width-16 shuffles, forms
+// the same b as its 15 neighbours in the stated order, and updates and stores its own row.  All f64, one rounding
+// per operation (contraction off), u_i * u_j commutes so M stays bitwise symmetric.  A group past N computes on
+// zeros and neither loads nor stores: no lane leaves before the barriers / shuffles.
+// The group's contiguous 2 KB goes through the LDS both ways: coalesced 16-B chunks (lane i takes chunks i, i + 16,
+// ...) into rows padded to 17 doubles, so that the 16 lanes' row reads and writes (8 B each, 34 dwords apart) fall
+// on distinct banks.  Lane i loading its row straight from global memory (8 x 16 B, lanes 128 B apart) measured
+// 0.8 us slower per launch at 4,096 envs and is not kept.
+using f64x2 = __attribute__((ext_vector_type(2))) double;
+constexpr int ELL_ENVS = 16, ELL_PITCH = EMB + 1;
+
+__global__ void __launch_bounds__(256)
+    elliptical_kernel(const int32_t* __restrict__ emb, const uint8_t* __restrict__ done, long long N, double ridge,
+                      double beta, double* __restrict__ minv, int32_t* __restrict__ count, double* __restrict__ eb,
+                      float* __restrict__ rewards, float* __restrict__ bonus) {
+    __shared__ double tile[ELL_ENVS * EMB * ELL_PITCH];
+    const int i = threadIdx.x & 15, g = threadIdx.x >> 4;
+    const long long n = (long long)blockIdx.x * ELL_ENVS + g;
+    const bool live = n < N;  // uniform over the 16-lane group
+    double phi[EMB], m[EMB], uj[EMB];
+#pragma unroll
+    for (int j = 0; j < EMB; ++j) phi[j] = m[j] = 0.0;
+    f64x2* __restrict__ mat = reinterpret_cast<f64x2*>(minv + (live ? n : 0) * (EMB * EMB));
+    double* __restrict__ mine = tile + g * EMB * ELL_PITCH;
+    if (live) {
+        const i32x4* qv = reinterpret_cast<const i32x4*>(emb + n * EMB);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const i32x4 q = qv[v];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) phi[4 * v + e] = (double)q[e];
+        }
+#pragma unroll
+        for (int k = 0; k < EMB / 2; ++k) {
+            const int c = k * 16 + i;  // chunk c = elements 2c, 2c + 1 = row c / 8, columns 2 (c % 8), + 1
+            const f64x2 x = mat[c];
+            mine[(c >> 3) * ELL_PITCH + 2 * (c & 7)] = x[0];
+            mine[(c >> 3) * ELL_PITCH + 2 * (c & 7) + 1] = x[1];
+        }
+    }
+    __syncthreads();
+    if (live) {
+#pragma unroll
+        for (int j = 0; j < EMB; ++j) m[j] = mine[i * ELL_PITCH + j];
+    }
+    double u = 0.0;
+#pragma unroll
+    for (int j = 0; j < EMB; ++j) u = u + m[j] * phi[j];
+#pragma unroll
+    for (int j = 0; j < EMB; ++j) uj[j] = __shfl(u, j, 16);
+    double b = 0.0;
+#pragma unroll
+    for (int j = 0; j < EMB; ++j) b = b + phi[j] * uj[j];
+    b = b > 0.0 ? b : 0.0;  // a NaN goes to 0 too
+    const double den = 1.0 + b;
+#pragma unroll
+    for (int j = 0; j < EMB; ++j) m[j] = m[j] - (u * uj[j]) / den;
+    bool reset = false;
+    if (live) {
+        reset = done[n] != 0;
+        if (i == 0) {
+            const int32_t c = count[n];
+            const double pay = c > 0 ? b : 0.0;  // an episode's first state is scored against no other
+            eb[n] = pay;
+            if (bonus) bonus[n] = (float)pay;
+            if (rewards) rewards[n] = rewards[n] + (float)(beta * pay);
+            count[n] = reset ? 0 : (c < 0x7FFFFFFF ? c + 1 : c);
+        }
+    }
+    if (reset) {
+        const double d = 1.0 / ridge;
+#pragma unroll
+        for (int j = 0; j < EMB; ++j) m[j] = j == i ? d : 0.0;
+    }
+    if (live) {
+#pragma unroll
+        for (int j = 0; j < EMB; ++j) mine[i * ELL_PITCH + j] = m[j];  // the row this lane read: no hazard
+    }
+    __syncthreads();
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < EMB / 2; ++k) {
+            const int c = k * 16 + i;
+            f64x2 x;
+            x[0] = mine[(c >> 3) * ELL_PITCH + 2 * (c & 7)];
+            x[1] = mine[(c >> 3) * ELL_PITCH + 2 * (c & 7) + 1];
+            mat[c] = x;
+        }
     }
 }
 
@@ -342,4 +484,28 @@ extern "C" int ppox_ngu_reward(const double* dk, const int32_t* kfound, const do
     ngu_reward_kernel<<<1, RT, 0, ppox::as_stream(stream)>>>(dk, kfound, mk, err, N, K, dm, em, decay, eps, xi, c, smax,
                                                              mod_max, int_rewards, bonus, modulator);
     PPOX_LAUNCHED("ppox_ngu_reward");
+}
+
+extern "C" int ppox_elliptical_bonus(const int32_t* emb, const uint8_t* done, int64_t N, double ridge, double beta,
+                                     double* minv, int32_t* count, double* eb, float* rewards, float* bonus,
+                                     void* stream) {
+    PPOX_REQUIRE(emb && done && minv && count && eb, "ppox_elliptical_bonus: null pointer");
+    PPOX_REQUIRE(N >= 1 && N <= 0x7FFFFFFFll, "ppox_elliptical_bonus: N must lie in [1, 2^31), not %lld",
+                 (long long)N);
+    PPOX_REQUIRE(std::isfinite(ridge) && ridge > 0.0, "ppox_elliptical_bonus: ridge must be finite and positive, not %g",
+                 ridge);
+    PPOX_REQUIRE(std::isfinite(beta), "ppox_elliptical_bonus: beta must be finite, not %g", beta);
+    elliptical_kernel<<<ppox::ceil_div(N, ELL_ENVS), 256, 0, ppox::as_stream(stream)>>>(emb, done, N, ridge, beta, minv,
+                                                                                        count, eb, rewards, bonus);
+    PPOX_LAUNCHED("ppox_elliptical_bonus");
+}
+
+extern "C" int ppox_ngu_modulate(const double* eb, const float* err, int64_t N, double* em, double mod_max,
+                                 float* int_rewards, float* bonus, float* modulator, void* stream) {
+    PPOX_REQUIRE(eb && em && int_rewards && bonus && modulator, "ppox_ngu_modulate: null pointer");
+    PPOX_REQUIRE(N >= 1 && N <= 0x7FFFFFFFll, "ppox_ngu_modulate: N must lie in [1, 2^31), not %lld", (long long)N);
+    PPOX_REQUIRE(mod_max >= 1.0, "ppox_ngu_modulate: mod_max must be at least 1, not %g", mod_max);
+    ngu_modulate_kernel<<<1, RT, 0, ppox::as_stream(stream)>>>(eb, err, N, em, mod_max, int_rewards, bonus,
+                                                               modulator);
+    PPOX_LAUNCHED("ppox_ngu_modulate");
 }

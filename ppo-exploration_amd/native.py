@@ -66,6 +66,8 @@ SIGNATURES = {
     "ppox_episodic_reward": [_vp, _vp, _vp, _i64, _i32, _vp, _f64, _f64, _f64, _f64, _f64, _f64, _vp, _vp, _vp],
     "ppox_ngu_reward": [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _f64, _f64, _f64, _f64, _f64, _f64, _vp, _vp, _vp,
                         _vp],
+    "ppox_elliptical_bonus": [_vp, _vp, _i64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ppox_ngu_modulate": [_vp, _vp, _i64, _vp, _f64, _vp, _vp, _vp, _vp],
     "ppox_gather_rows": [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp],
     "ppox_grad_sumsq": [_vp, _i64, _vp, _vp],
     "ppox_adam_step": [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _f64, _f64, _f64, _f64, _i64, _vp, _vp],
@@ -493,6 +495,22 @@ def ngu_reward(dk, kfound, mk, err, N, K, dm, em, decay, eps, xi, c, smax, mod_m
     (N,) f32 written.  include/ppox.h has the semantics."""
     call("ppox_ngu_reward", _p(dk), _p(kfound), _p(mk), _p(err), N, K, _p(dm), _p(em), decay, eps, xi, c, smax,
          mod_max, _p(int_rewards), _p(bonus), _p(modulator), stream_ptr(stream))
+
+
+def elliptical_bonus(emb, done, N, ridge, beta, minv, count, eb, rewards=None, bonus=None, stream=None):
+    """The elliptical episodic bonus of one step: eb (N,) f64 = emb' minv emb (0 on an episode's first step), then
+    minv (N, 16, 16) f64 advanced by the rank-one update (reset to diag(1 / ridge) where done (N,) uint8 is set)
+    and count (N,) int32 advanced; bonus (N,) f32 written and rewards (N,) f32 += beta * eb where given.
+    include/ppox.h has the semantics."""
+    call("ppox_elliptical_bonus", _p(emb), _p(done), N, ridge, beta, _p(minv), _p(count), _p(eb), _p(rewards),
+         _p(bonus), stream_ptr(stream))
+
+
+def ngu_modulate(eb, err, N, em, mod_max, int_rewards, bonus, modulator, stream=None):
+    """ngu_reward's modulator for the bonus eb (N,) f64 that is already there: em (3,) f64 advanced (err None:
+    modulator 1, em untouched), bonus, modulator and int_rewards = eb * modulator (N,) f32 written."""
+    call("ppox_ngu_modulate", _p(eb), _p(err), N, _p(em), mod_max, _p(int_rewards), _p(bonus), _p(modulator),
+         stream_ptr(stream))
 
 
 def categorical_sample(logits, N, A, env_offset, seed, counter, actions, log_probs, stream=None):

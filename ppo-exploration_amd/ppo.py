@@ -13,8 +13,8 @@ object; default: the synthetic env for env_id), quiet, dynamics ("synthetic";
 KeyDoor-v0, whose visit-count table learn() logs as rollout/coverage), sil_kwargs (PPO(sil=True):
 size, alpha, beta, epochs, batch of the self-imitation module, sil_module.py), episodic / episodic_kwargs
 (PPO(episodic=True): a per-episode kNN novelty bonus on the uint8 frames; k, capacity, beta, eps,
-xi, c, smax, decay, frames).  PPO_NGU is PPO_RND with that bonus times an RND modulator as its
-intrinsic reward.
+xi, c, smax, decay, frames; or kind="elliptical" with ridge, beta, frames: the elliptical bonus of DESIGN.md §4.7).
+PPO_NGU is PPO_RND with that bonus times an RND modulator as its intrinsic reward.
 
 Per iteration on each rank:
   collect: T x [net forward (rocBLAS + MFMA convs) -> ppox_categorical_sample ->
@@ -471,7 +471,8 @@ class BaseAlgorithm:
         if getattr(self.rollout, "do_episodic", False):
             # the rollout's mean bonus (before beta) and the running mean squared kNN distance (two host reads)
             logger.record("rollout/episodic_bonus", float(self.rollout.episodic_bonus.mean().item()))
-            logger.record("rollout/episodic_dm", float(self.rollout.dm[0].item()))
+            if hasattr(self.rollout, "dm"):                 # kind="knn" alone has the running mean
+                logger.record("rollout/episodic_dm", float(self.rollout.dm[0].item()))
             if hasattr(self.rollout, "ngu_modulator"):
                 logger.record("rollout/ngu_modulator", float(self.rollout.ngu_modulator.mean().item()))
         if extra:
@@ -564,12 +565,13 @@ class PPO(BaseAlgorithm):
 
     def _episodic_config(self, episodic, kw):
         """episodic_kwargs (k, capacity, beta, eps, xi, c, smax, decay, frames: buffer.EPISODIC_DEFAULTS) for the
-        storage, None without the bonus; capacity defaults to the env's max_len where it has one."""
+        storage, None without the bonus; capacity defaults to the env's max_len where it has one.  With
+        kind="elliptical" (buffer.ELLIPTICAL_DEFAULTS: ridge, beta, frames) there is no ring and no capacity."""
         if not episodic:
             return None
         cfg = dict(kw or {})
         max_len = getattr(self.env, "max_len", None)
-        if "capacity" not in cfg and max_len is not None:
+        if cfg.get("kind", "knn") == "knn" and "capacity" not in cfg and max_len is not None:
             cfg["capacity"] = int(max_len)
         return cfg
 
@@ -704,7 +706,7 @@ class PPO(BaseAlgorithm):
     def learn(self, total_timesteps, log_interval, reward_target=None, log_to_file=False):
         name = "PPO_SimHash" if self.sim_hash else ("PPO_SIL" if self.sil else "PPO")
         if self.episodic:
-            name = "PPO_Episodic"
+            name = "PPO_Elliptical" if self.rollout.epi_kind == "elliptical" else "PPO_Episodic"
         return self._learn(name, total_timesteps, log_interval, reward_target, log_to_file)
 
 
@@ -888,7 +890,8 @@ class PPO_NGU(PPO_RND):
     per-episode kNN bonus of PPO(episodic=True) times a modulator in [1, mod_max] from the RND error's running
     moments, paid as the intrinsic reward (own value head, non-episodic return, separately normalised advantage)
     while the rewards stay the env's own.  PPO_RND's keywords plus episodic_kwargs (k, capacity, eps, xi, c, smax,
-    decay, frames, mod_max: buffer.NGU_DEFAULTS; capacity defaults to the env's max_len where it has one) and
+    decay, frames, mod_max: buffer.NGU_DEFAULTS; capacity defaults to the env's max_len where it has one; or
+    kind="elliptical" with ridge, frames, mod_max: the elliptical bonus of DESIGN.md §4.7 in the kNN bonus's place) and
     int_adv_coef, the weight of the normalised intrinsic advantage in the loss.
 
     Both bonuses of step t are of obs_slots[t], the observation the action was taken in (PPO(episodic=True)'s
@@ -909,7 +912,7 @@ class PPO_NGU(PPO_RND):
     def _rollout_kwargs(self):
         cfg = dict(self._ngu_kwargs)
         max_len = getattr(self.env, "max_len", None)
-        if "capacity" not in cfg and max_len is not None:
+        if cfg.get("kind", "knn") == "knn" and "capacity" not in cfg and max_len is not None:
             cfg["capacity"] = int(max_len)
         return {"episodic": cfg, "hash_seed": self.seed}
 
@@ -926,7 +929,8 @@ class PPO_NGU(PPO_RND):
             ro.ngu(ro.obs_slots[t], ro.masks[t], ro.rnd_err[t], t)
 
     def learn(self, total_timesteps, log_interval, reward_target=None, log_to_file=False):
-        return self._learn("PPO_NGU", total_timesteps, log_interval, reward_target, log_to_file)
+        name = "PPO_NGU_Elliptical" if self.rollout.epi_kind == "elliptical" else "PPO_NGU"
+        return self._learn(name, total_timesteps, log_interval, reward_target, log_to_file)
 
 
 class PPO_ICM(BaseAlgorithm):

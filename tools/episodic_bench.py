@@ -92,6 +92,8 @@ def step_times(args):
                 "three_launches": timed(lambda: st.episodic(obs[0], rewards, never, 0), args.launches, args.warmup,
                                         before=put_back)}
         del st
+        if args.kind == "elliptical":
+            res.update(elliptical_step_times(args, env, obs, frames, err, em, ngu_out))
     # the yardsticks, on the same frames
     hs = buffer.RolloutStorage(1, n, env.observation_space, env.action_space, sim_hash=True)
     xs = obs[0].reshape(n, -1)
@@ -103,9 +105,49 @@ def step_times(args):
     return res
 
 
+def elliptical_step_times(args, env, obs, frames, err, em, ngu_out):
+    """kind="elliptical"  in the same process on the same frames: sums, ppox_elliptical_bonus (with
+    the reward add, and bare as PPO_NGU launches it), ppox_ngu_modulate and the two launches together, 8 steps into
+    the episode and --capacity steps into it (the matrices dense).  The bonus kernel moves 2 x 2 KB per env."""
+    n = args.n_envs
+    st = buffer.RolloutStorage(1, n, env.observation_space, env.action_space,
+                               episodic=dict(kind="elliptical", frames=frames))
+    x = obs[0].reshape(n, -1)[:, st.epi_offset:]
+    actions = torch.zeros(n, dtype=torch.int32, device="cuda")
+    rewards, dones = torch.zeros(n, device="cuda"), torch.zeros(n, dtype=torch.uint8, device="cuda")
+    never = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    dret, dlen = torch.empty(n, device="cuda"), torch.empty(n, dtype=torch.int32, device="cuda")
+    sums = lambda: native.simhash_sums_u8(x, n, st.epi_D, x.stride(0), st.epi_A8, st.epi_rowsum,  # noqa: E731
+                                          st.epi_workspace, st.epi_emb)
+    ell = lambda: native.elliptical_bonus(st.epi_emb, never, n, st.epi_ridge, st.epi_beta, st.minv,  # noqa: E731
+                                          st.count, st.eb, rewards, st.episodic_bonus[0])
+    bare = lambda: native.elliptical_bonus(st.epi_emb, never, n, st.epi_ridge, 0.0, st.minv, st.count,  # noqa: E731
+                                           st.eb)
+    mod = lambda e: native.ngu_modulate(st.eb, e, n, em, 5.0, ngu_out[0], ngu_out[1], ngu_out[2])  # noqa: E731
+    res, moved, done_steps = {}, 2 * n * 16 * 16 * 8, 0
+    for phase, upto in (("early_8_steps", 8), ("late", args.capacity)):
+        for j in range(done_steps, upto):
+            env.step_into(obs[j % 2], obs[1 - j % 2], actions.random_(0, 5), rewards, dones, dret, dlen)
+            st.episodic(obs[1 - j % 2], rewards, never, 0)
+        done_steps = upto
+        r = {"sums": timed(sums, args.launches, args.warmup),
+             "elliptical_bonus": timed(ell, args.launches, args.warmup),
+             "elliptical_bonus_bare": timed(bare, args.launches, args.warmup),
+             "ngu_modulate": timed(lambda: mod(err), args.launches, args.warmup),
+             "ngu_modulate_no_err": timed(lambda: mod(None), args.launches, args.warmup),
+             "two_launches": timed(lambda: st.episodic(obs[0], rewards, never, 0), args.launches, args.warmup)}
+        r["elliptical_bonus_GBps_at_median"] = round(moved / r["elliptical_bonus"]["median_us"] * 1e-3, 1)
+        res[f"elliptical/{frames}/{phase}"] = r
+    res[f"elliptical/{frames}/state_finite"] = bool(torch.isfinite(st.minv).all().item())
+    return res
+
+
 def iteration_times(args):
     res = {}
-    for name, kw in (("PPO", {}), ("PPO_episodic", dict(episodic=True))):
+    configs = [("PPO", {}), ("PPO_episodic", dict(episodic=True))]
+    if args.kind == "elliptical":
+        configs.append(("PPO_elliptical", dict(episodic=True, episodic_kwargs=dict(kind="elliptical"))))
+    for name, kw in configs:
         np.random.seed(0)
         torch.manual_seed(0)
         env = E.make_env("KeyDoor-v0", n_envs=args.n_envs, seed=0, dynamics="real", max_len=args.capacity)
@@ -132,6 +174,11 @@ def iteration_times(args):
     res["episodic_over_plain_iteration"] = round(res["PPO_episodic"]["iteration_ms"] / res["PPO"]["iteration_ms"], 4)
     res["collect_added_us_per_step"] = round((res["PPO_episodic"]["collect_ms"] - res["PPO"]["collect_ms"])
                                              / args.nstep * 1e3, 2)
+    if args.kind == "elliptical":
+        res["elliptical_over_plain_iteration"] = round(res["PPO_elliptical"]["iteration_ms"]
+                                                       / res["PPO"]["iteration_ms"], 4)
+        res["elliptical_collect_added_us_per_step"] = round(
+            (res["PPO_elliptical"]["collect_ms"] - res["PPO"]["collect_ms"]) / args.nstep * 1e3, 2)
     return res
 
 
@@ -147,6 +194,8 @@ def main():
     ap.add_argument("--iterations", type=int, default=3)
     ap.add_argument("--iter-warmup", type=int, default=2)
     ap.add_argument("--no-iterations", action="store_true", help="the step's launches only")
+    ap.add_argument("--kind", choices=("knn", "elliptical"), default="knn",
+                    help="elliptical: the kind='elliptical' launches and learn() iteration beside the kNN ones")
     ap.add_argument("--out", default=os.path.join("profiles", "episodic", "step_time.json"))
     args = ap.parse_args()
     out = {"device": torch.cuda.get_device_name(0), "config": {k: v for k, v in vars(args).items() if k != "out"},

@@ -1,4 +1,5 @@
-"""PPO, PPO(sim_hash=True), PPO_RND, PPO_ICM, PPO(episodic=True) and PPO_NGU (defaults, and int_adv_coef=0.3) on
+"""PPO, PPO(sim_hash=True), PPO_RND, PPO_ICM, PPO(episodic=True) and PPO_NGU (defaults, and int_adv_coef=0.3), and the
+last two with the elliptical bonus (PPO_E3B, PPO_NGU_E3B), on
 KeyDoor-v0 for a fixed number of env steps and three seeds. Every run is a fresh child process under its own `timeout`; its log points (env steps,
 ep_rew_mean — the mean return of the last 50 episodes, which on this task is the goal rate —, coverage) go as one
 JSON line each into --out, after one line per seed with the numpy twin's random-policy goal rate at that seed and
@@ -23,6 +24,9 @@ CONFIGS = {
     "PPO_Episodic": ("PPO", {"episodic": True}),  # the defaults: k 10, capacity max_len, the newest frame
     "PPO_NGU": ("PPO_NGU", {}),                   # the same episodic defaults, mod_max 5, int_adv_coef 1
     "PPO_NGU_0.3": ("PPO_NGU", {"int_adv_coef": 0.3}),
+    # the elliptical bonus at its defaults: ridge 2^30, beta 0.1 / mod_max 5, the newest frame
+    "PPO_E3B": ("PPO", {"episodic": True, "episodic_kwargs": {"kind": "elliptical"}}),
+    "PPO_NGU_E3B": ("PPO_NGU", {"episodic_kwargs": {"kind": "elliptical"}}),
 }
 
 
@@ -50,7 +54,9 @@ def child(args):
                "ep_rew_mean": kv.get("rollout/ep_rew_mean"), "episodes": kv.get("rollout/num_episodes"),
                "coverage": kv["rollout/coverage"], "seconds": round(time.time() - t0, 2)}
         if "rollout/episodic_bonus" in kv:
-            row.update(episodic_bonus=kv["rollout/episodic_bonus"], episodic_dm=kv["rollout/episodic_dm"])
+            row.update(episodic_bonus=kv["rollout/episodic_bonus"])
+        if "rollout/episodic_dm" in kv:                    # kind="knn" alone
+            row.update(episodic_dm=kv["rollout/episodic_dm"])
         if "rollout/ngu_modulator" in kv:
             row.update(ngu_modulator=kv["rollout/ngu_modulator"], mean_int_reward=kv["rollout/mean_int_reward"])
         print(json.dumps(row), flush=True)
